@@ -12,12 +12,17 @@ timed region.
 `--gpus N` (N > 1) without a launcher's WORLD_SIZE starts
 `torch.distributed.run --nproc-per-node N` on this script as a CHILD process
 before anything touches the GPU, and exits with its return code; rank 0's JSON
-line reaches stdout through the inherited descriptor.  With N > 1 the line
-also carries BASELINE configs[3] (FLAT IP, 1536-d, 12.5M rows per GPU: the
-full 100M part at N = 8, a labelled 12.5M x N subset below) searched through
-the same sharded path.
+line reaches stdout through the inherited descriptor.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task README).
+A plain run sets up, warms up, times `--steps` steps, writes the last step's
+output if `--dump-outputs DIR` is given, and prints ONE JSON line on rank 0
+(see the driver contract in the task README).  `--full` adds every other leg
+after the timed region: the exact-path check of the timed output, the HBM read
+sweep, the nq sweep, the CPU baseline, the index and the further BASELINE
+configurations; with N > 1 the small-batch sharded points and BASELINE
+configs[3] (FLAT IP, 1536-d, 12.5M rows per GPU: the full 100M part at N = 8,
+a labelled 12.5M x N subset below) searched through the same sharded path,
+printed as a second line after the headline.
 """
 import argparse
 import json
@@ -56,8 +61,13 @@ def parse():
                     help="configs[3] rows per rank (default: 12.5M per GPU, the full 100M part at N = 8)")
     ap.add_argument("--inject-leg-failure", default="",
                     help="testing: 'config3:R' makes rank R fail the configs[3] leg (fail-soft drill)")
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (exact-path check, HBM read sweep, nq sweep, "
+                         "CPU baseline, index, further configs; N > 1: the sharded legs); the --no-* options trim them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned to DIR/ids.npy (float64) and DIR/dist.npy (float32)")
     ap.add_argument("--n", type=int, default=10_000_000)
     ap.add_argument("--d", type=int, default=768)
     ap.add_argument("--nq", type=int, default=1000)
@@ -88,7 +98,10 @@ def parse():
                     help="settings timed on the second distribution")
     ap.add_argument("--index-pmc", default=None,
                     help="JSON {mode: pmc_traffic.py output} of k_ivf_scan at each distribution's operating point")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -913,6 +926,22 @@ def emit(result):
     print(json.dumps(out), flush=True)
 
 
+def dump_outputs(path, ids, dst):
+    """--dump-outputs: the (ids, distances) the last timed step returned to
+    its caller (nq x k each) as float64 ids and float32 distances; above
+    64 MB in all, a fixed seeded sample of the queries' rows (rows.npy)."""
+    os.makedirs(path, exist_ok=True)
+    gi, gd = ids.cpu().numpy(), dst.cpu().numpy()
+    nq, k = gi.shape
+    keep = max(1, (60 << 20) // (12 * k + 8))
+    if nq > keep:
+        rows = np.sort(np.random.default_rng(0x5EED0004).choice(nq, size=keep, replace=False))
+        gi, gd = gi[rows], gd[rows]
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "ids.npy"), gi.astype(np.float64))
+    np.save(os.path.join(path, "dist.npy"), gd.astype(np.float32))
+
+
 def run_leg(result, name, fn):
     """An optional single-GPU leg: its failure is recorded in the line
     instead of losing the line."""
@@ -965,8 +994,8 @@ def rank_main(ctx, args, comm, exchange, loopback=0):
     """N > 1 (processes over RCCL, or threads over the loopback transport):
     each rank searches its granule-aligned row-range shard of the configs[1]
     part, the per-shard top-k are exchanged and merged inside libmqvs.  Rank
-    0 prints the headline line as soon as it is measured, then the line again
-    with the optional legs (a leg failing on any rank is recorded, not fatal)."""
+    0 prints the headline line as soon as it is measured, then (--full) the line
+    again with the optional legs (a leg failing on any rank is recorded, not fatal)."""
     import torch
     import myscaledb_amd as mq
     import myscaledb_amd.vector_scan as mq_scan
@@ -1026,8 +1055,10 @@ def rank_main(ctx, args, comm, exchange, loopback=0):
 
     # exactness at full size, outside the timed region: the timed (merged)
     # output against the same sharded search on every rank's exact fp32 path
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, f_ids, f_dst)  # (the merged result, the same on every rank)
     exact = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         def check():
             ctx.process_wide(lambda: mq_scan.set_batch_mode(1))
             try:
@@ -1063,10 +1094,11 @@ def rank_main(ctx, args, comm, exchange, loopback=0):
             result["fast_path_calls"] = after["fast_calls"] - before["fast_calls"]
             result["redo_calls"] = after["redo_calls"] - before["redo_calls"]
         emit(result)  # the headline first: a later leg cannot lose it
-    legs = sharded_legs(ctx, mq, mq_scan, comm, seg, args) if comm is not None else {}
-    if rank == 0:
-        result.update(legs)
-        emit(result)
+    if args.full:
+        legs = sharded_legs(ctx, mq, mq_scan, comm, seg, args) if comm is not None else {}
+        if rank == 0:
+            result.update(legs)
+            emit(result)
     ctx.barrier()
     seg.free()
     return 0
@@ -1150,6 +1182,13 @@ def single_main(args):
                  2.0 * nq * n * d / (FP32_MFMA_PEAK_TFLOPS * 1e12))
     roof["survey_t_star_ms"] = round(t_star * 1e3, 3)
     roof["survey_t_star_over_t"] = round(t_star * 1e3 / ms, 3)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ids, dst)
+    if not args.full:
+        # a plain run: the headline only (every other leg is behind --full)
+        seg.free()
+        emit(headline(args, ms, st, roof, None, 1, None, 1))
+        return
     # exactness at full size, outside the timed region: the timed path's
     # output against the exact fp32 path on every query
     exact = None if args.no_verify else exact_check(mq_scan, seg, q, k, ids, dst)

@@ -1,5 +1,5 @@
 """bench.py's N-rank sequence rehearsed on ONE GPU:
-`--loopback 8` runs what `--gpus 8` runs on every rank -- the configs[1]
+`--full --loopback 8` runs what `--full --gpus 8` runs on every rank -- the configs[1]
 sharded step, the small-batch sharded points and a reduced configs[3] leg --
 as 8 threads over a loopback communicator (mqvs_comm_init_loopback), i.e.
 the same mqvs_sharded_search code an RCCL communicator runs
@@ -17,7 +17,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--loopback", "8", "--steps", "2", "--warmup", "1", "--n", "2000000", "--nq", "300",
+SMALL = ["--full", "--loopback", "8", "--steps", "2", "--warmup", "1", "--n", "2000000", "--nq", "300",
          "--config3-rows", "200000"]
 
 

@@ -10,6 +10,8 @@ rc=$?; echo "pytest rc=$rc"; tail -4 gpurun_out/gpu_tests.log
 timeout -k 10 300 python -u tools/binary_sweep.py > gpurun_out/binary_sweep.jsonl 2> gpurun_out/binary_sweep.err
 echo "sweep rc=$?"; cut -c1-330 gpurun_out/binary_sweep.jsonl
 [ "$1" = "--no-bench" ] && exit 0
-timeout -k 10 300 python -u bench.py --no-cpu --no-verify "$@" > gpurun_out/bench_quick.json 2> gpurun_out/bench_quick.err
+B=${MQVS_OUT:-bench_out}  # the bench line and its stderr
+mkdir -p "$B"
+timeout -k 10 300 python -u bench.py --full --no-cpu --no-verify "$@" > "$B/bench_quick.json" 2> "$B/bench_quick.err"
 echo "bench rc=$?"; python -c "
-import json; r=json.load(open('gpurun_out/bench_quick.json')); print(r['value'], r['ms_per_step'], r['stats_last_step']); print(r.get('index',{}).get('points'))"
+import json; r=json.load(open('$B/bench_quick.json')); print(r['value'], r['ms_per_step'], r['stats_last_step']); print(r.get('index',{}).get('points'))"

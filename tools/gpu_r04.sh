@@ -14,7 +14,7 @@ if [ "$what" = tests ] || [ "$what" = all ]; then
   [ $rc -ne 0 ] && exit 1
 fi
 if [ "$what" = bench ] || [ "$what" = all ]; then
-  timeout -k 10 400 python -u bench.py --steps 10 --warmup 3 --no-index --no-configs --no-config1-points \
+  timeout -k 10 400 python -u bench.py --full --steps 10 --warmup 3 --no-index --no-configs --no-config1-points \
     --no-cpu --no-small --read-sweep-gib 0 "$@" > gpurun_out/bench_quick.json 2> gpurun_out/bench_quick.err
   rc=$?
   echo "bench rc=$rc"; tail -3 gpurun_out/bench_quick.err

@@ -9,7 +9,7 @@ if [ "${1:-tests}" = tests ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/gpu_tests.log 2>&1
   rc=$?; echo "pytest rc=$rc"; tail -3 $O/gpu_tests.log; [ $rc -ne 0 ] && exit 1
 fi
-timeout -k 10 600 python -u bench.py --steps 5 --warmup 2 --no-index --no-config1-points --no-cpu --no-small \
+timeout -k 10 600 python -u bench.py --full --steps 5 --warmup 2 --no-index --no-config1-points --no-cpu --no-small \
   --read-sweep-gib 0 --no-verify > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
 python3 - <<'PY'
 import json

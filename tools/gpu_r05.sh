@@ -30,9 +30,9 @@ for step in "$@"; do
               timeout -k 10 400 python -u tools/index_scan_ab.py --mode $m --search "${IDX_SEARCH:-nprobe=1}" --tunes "$IDX_TUNES" > $O/idx_ab$m.jsonl 2> $O/idx_ab$m.err || exit 1
               cat $O/idx_ab$m.jsonl
             done ;;
-    bench_quick) timeout -k 10 300 python bench.py --steps 5 --warmup 2 --no-index --no-configs --no-config1-points --no-cpu > $O/bench_quick.json 2> $O/bench_quick.err || exit 1
+    bench_quick) timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --no-index --no-configs --no-config1-points --no-cpu > $O/bench_quick.json 2> $O/bench_quick.err || exit 1
                  python3 -c "import json;d=json.loads(open('$O/bench_quick.json').readlines()[-1]);print(d['value'],d['ms_per_step'],d['roofline']);print([ (x['nq'],x['ms_per_search'],x['hbm_frac_end_to_end']) for x in d['small_batch']])" ;;
-    bench) timeout -k 10 900 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || exit 1 ;;
+    bench) timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || exit 1 ;;
     gather_ab) timeout -k 10 400 python tools/gather_source_ab.py --nq 1,16 --sel 1,10 > $O/gather_ab.jsonl 2> $O/gather_ab.err || exit 1 ;;
     seg_ab) timeout -k 10 600 python -u tools/ab_split.py --dbg --nqs 1 --metrics Cosine --modes 1 --splits 2 --reps 10 \
               --tunes 'MQVS_SEG=8,4,65536;MQVS_SEG=8,16,65536;MQVS_SEG=8,64,65536;MQVS_SEG=32,64,65536;MQVS_SEG=8,4,65536' \

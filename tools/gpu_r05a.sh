@@ -7,7 +7,7 @@ O=gpurun_out/r5a
 mkdir -p $O
 timeout -k 10 700 python -u -m pytest tests -m gpu -q --maxfail=5 --timeout 300 --timeout-method thread > $O/tests.log 2>&1
 echo "tests_rc=$?"; tail -3 $O/tests.log
-timeout -k 10 300 python bench.py --steps 5 --warmup 2 --no-index --no-configs --no-config1-points --no-cpu > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --no-index --no-configs --no-config1-points --no-cpu > $O/bench.json 2> $O/bench.err
 echo "bench_rc=$?"
 timeout -k 10 400 python tools/gather_source_ab.py > $O/gather_ab.jsonl 2> $O/gather_ab.err
 echo "gather_rc=$?"

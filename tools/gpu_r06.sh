@@ -47,7 +47,7 @@ for step in "$@"; do
       [ -f $O/pmc_traffic.json ] && PA+=(--pmc $O/pmc_traffic.json)
       [ -f $O/pmc_nq1.json ] && PA+=(--pmc-nq1 $O/pmc_nq1.json)
       [ -f $O/index_pmc.json ] && PA+=(--index-pmc $O/index_pmc.json)
-      timeout -k 10 900 python -u bench.py "${PA[@]}" > $O/bench.json 2> $O/bench.err || { echo "bench failed rc=$?"; tail -30 $O/bench.err; exit 1; }
+      timeout -k 10 900 python -u bench.py --full "${PA[@]}" > $O/bench.json 2> $O/bench.err || { echo "bench failed rc=$?"; tail -30 $O/bench.err; exit 1; }
       head -c 3000 $O/bench.json; echo
       ( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$O/prof" -o run --output-format csv \
           -- python "$GRAFT_REPO_ROOT/bench.py" --steps 3 --warmup 1 --no-cpu --no-verify --no-index --no-configs \
