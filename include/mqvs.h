@@ -412,6 +412,70 @@ int mqvs_index_search(mqvs_index_t idx, const float *queries, int32_t nq, int32_
  *   approximate value (the centroid list pass). */
 int mqvs_index_centroids(mqvs_index_t idx, float *out, int64_t cap);
 int mqvs_index_probes(mqvs_index_t idx, const float *queries, int32_t nq, const char *params, int64_t *out_probes);
+
+/* ---- binary vector index (the reference's BINARYMSTG seam, KAT 00038) ------
+ * mqvs_index_build on a binary segment (mqvs_segment_create_binary) with
+ * index_type "BINARYMSTG" (also accepted: "BINARYIVF"; case-insensitive, NULL
+ * = BINARYMSTG on a binary segment).  A float index type on a binary segment,
+ * or a binary type on a float segment, fails with MQVS_ERR_LOGICAL.  MSTG's
+ * code is absent from the reference snapshot; this is the library's own
+ * design: an inverted file over k-majority (Hamming k-means) lists, the codes
+ * copied in list order ([npos][code words], 16-B aligned rows), a popcount
+ * scan of the lists each query probes.  Binary distances are exact integers
+ * (Jaccard: one fp32 division of two integers), so the scan computes the
+ * final distance: there is no approximate stage, no re-rank and no tolerance.
+ * Every returned distance is bit-identical to mqvs_search_binary's on the
+ * same row, and a search that probes every list equals mqvs_search_binary bit
+ * for bit.
+ * Build params: metric_type (Hamming | Jaccard, default the segment's; other
+ * metrics MQVS_ERR_NOT_IMPLEMENTED), alpha, nlist, kmeans_iters, sample --
+ * defaults and ranges as above.  The list count is never chosen from the data.
+ * Parts of 2^31 or more rows are MQVS_ERR_NOT_IMPLEMENTED.  The build is
+ * integer arithmetic only, hence deterministic.  The coarse metric is Hamming
+ * for both metrics (Jaccard parts are partitioned by Hamming, scanned with
+ * Jaccard):
+ *   sample       rows floor(i n / S), i < S; initial centroids are sample rows
+ *                floor(c S / L), c < L
+ *   iteration    each sample row goes to the centroid at the smallest Hamming
+ *                distance (ties: the lowest list id); each centroid bit is
+ *                then set iff 2 ones > members (majority, tie -> 0); a list
+ *                with no members keeps its centroid
+ *   assignment   every row to its nearest centroid by the same rule (distance
+ *                == dim_bits included); lists hold their rows in ascending
+ *                order
+ * mqvs_index_info: dim = dim_bits, npos = rows (no padding positions),
+ * hbm_bytes counts the list-ordered code copy.  mqvs_index_free,
+ * mqvs_index_set_row_ids_map and mqvs_cache_put / acquire work as for float
+ * indexes.
+ *
+ * mqvs_index_search_binary: queries are nq x dim_bits / 8 bytes.  Params:
+ *   alpha, nprobe   as mqvs_index_search (nprobe <= min(nlist, 4096); nprobe ==
+ *                   nlist probes every list with no ranking; the default
+ *                   searches a part of up to 4 lists exhaustively)
+ *   metric          Hamming | Jaccard (default the index's; either may be
+ *                   searched, as mqvs_search_binary allows)
+ *   num_reorder     accepted and ignored (the scan is exact)
+ * The nprobe nearest centroids by (Hamming, list id) are probed.  Output
+ * exactly as mqvs_search_binary: ascending by (distance, row), Hamming as
+ * float counts, rows at Hamming distance == dim_bits never returned, -1 /
+ * FLT_MAX padding, row_offset applied; a registered row_ids_map is applied
+ * last.  MQVS_F_DEVICE_PTRS / MQVS_F_ASYNC as mqvs_index_search;
+ * MQVS_F_FIRST_STAGE is accepted and returns the same exact result.
+ * mqvs_index_search on a binary index, and this call on a float index, fail
+ * with MQVS_ERR_LOGICAL.  mqvs_index_last_stats after it: coarse / scan /
+ * select times, values = records kept by the scan (positions that pass the
+ * filter and the distance rule), items, plane_bytes = code bytes of the probed
+ * lists, pairs; plan_ms, rerank_ms and reranked are 0.
+ * mqvs_index_centroids_binary: the nlist x dim_bits / 8 centroid bytes into
+ *   host memory (cap_bytes = bytes out holds).
+ * mqvs_index_probes_binary: as mqvs_index_probes for host binary queries; the
+ *   lists are the exact top nprobe by (Hamming distance, list id). */
+int mqvs_index_search_binary(mqvs_index_t idx, const uint8_t *queries, int32_t nq, int32_t k, const char *params,
+                             const uint8_t *filter, const uint8_t *row_exists, int64_t *out_ids, float *out_dist,
+                             uint32_t flags, mqvs_stream_t stream);
+int mqvs_index_centroids_binary(mqvs_index_t idx, uint8_t *out, int64_t cap_bytes);
+int mqvs_index_probes_binary(mqvs_index_t idx, const uint8_t *queries, int32_t nq, const char *params,
+                             int64_t *out_probes);
 /* Decoupled parts: a part merged from several source parts whose index still
  * serves the source part's rows (the reference's VIWithMeta row_ids_map /
  * inverted maps, VICacheObject.h:50-64).

@@ -492,6 +492,145 @@ private:
     std::shared_ptr<IndexHandle> idx;
 };
 
+/// One data part's FixedString(N) binary vector column resident on a GPU
+/// (vectorScanWithoutIndex<BinaryVector>, MergeTreeVSManager.cpp:1188-1273,
+/// 1395-1425).
+class BinaryPartScan
+{
+public:
+    /// codes: n * nbytes FixedString bytes, row-major; dimension = 8 nbytes bits.
+    BinaryPartScan(const uint8_t * codes, int64_t n, int32_t nbytes, int mqvs_metric, int64_t granule_rows,
+                   int64_t row_offset = 0, int device = 0)
+    {
+        if (mqvs_metric != MQVS_METRIC_HAMMING && mqvs_metric != MQVS_METRIC_JACCARD)
+            throw DB::Exception(DB::ErrorCodes::NOT_IMPLEMENTED, "{}",
+                                std::string("Metric not implemented in brute force search for Binary Vector"));
+        check(mqvs_init(device));
+        mqvs_segment_t s = nullptr;
+        check(mqvs_segment_create_binary(codes, n, 8 * nbytes, mqvs_metric, granule_rows, row_offset, 0, &s));
+        adopt(s, true);
+    }
+
+    /// A view of a segment owned elsewhere (a PartCache entry).
+    static BinaryPartScan borrow(mqvs_segment_t s) { return BinaryPartScan(s, false); }
+
+    int32_t dimension() const { return dim_bits; }
+    int32_t codeBytes() const { return dim_bits / 8; }
+    int64_t rows() const { return n; }
+    int64_t rowOffset() const { return row_offset; }
+    int metricId() const { return metric; }
+    mqvs_segment_t handle() const { return seg->h; }
+    mqvs_segment_t release() const
+    {
+        seg->owned = false;
+        return seg->h;
+    }
+
+    /// "The dimension of searched index and input doesn't match." for a query
+    /// of another FixedString length (LOGICAL_ERROR, as the float seam).
+    void checkCodeBytes(int32_t query_bytes) const
+    {
+        if (query_bytes != codeBytes())
+            throw DB::Exception(DB::ErrorCodes::LOGICAL_ERROR, "{}",
+                                std::string("The dimension of searched index and input doesn't match."));
+    }
+
+    /// nq*k ids / distances ascending by (distance, row), -1 / FLT_MAX padded;
+    /// mqvs_metric: Hamming or Jaccard (either may be searched).
+    void search(const uint8_t * queries, int32_t nq, int32_t query_bytes, int32_t k, int mqvs_metric,
+                const uint8_t * filter, const uint8_t * row_exists, int64_t * ids, float * dist) const
+    {
+        checkCodeBytes(query_bytes);
+        if (mqvs_metric != MQVS_METRIC_HAMMING && mqvs_metric != MQVS_METRIC_JACCARD)
+            throw DB::Exception(DB::ErrorCodes::NOT_IMPLEMENTED, "{}",
+                                std::string("Metric not implemented in brute force search for Binary Vector"));
+        check(mqvs_search_binary(seg->h, queries, nq, k, mqvs_metric, filter, row_exists, ids, dist, 0, nullptr));
+    }
+
+private:
+    BinaryPartScan(mqvs_segment_t s, bool owned) { adopt(s, owned); }
+
+    void adopt(mqvs_segment_t s, bool owned)
+    {
+        seg = std::make_shared<SegmentHandle>(s, owned);
+        int32_t d = 0, m = 0;
+        check(mqvs_segment_info(s, &n, &d, &m, nullptr, &row_offset, nullptr));
+        dim_bits = d;
+        metric = m;
+    }
+
+    std::shared_ptr<SegmentHandle> seg;
+    int64_t n = 0;
+    int64_t row_offset = 0;
+    int32_t dim_bits = 0;
+    int metric = 0;
+};
+
+/// The binary vector index of one part's FixedString column (the reference's
+/// BINARYMSTG, KAT 00038) over a resident BinaryPartScan, which must outlive
+/// it.  Distances are exact: every result row carries mqvs_search_binary's
+/// distance, and a search probing every list equals BinaryPartScan::search.
+class BinaryGpuIndex
+{
+public:
+    /// index_type: "BINARYMSTG" or "BINARYIVF"; params: "key=value,..." as
+    /// include/mqvs.h documents (metric_type, alpha, nlist, kmeans_iters, sample).
+    BinaryGpuIndex(const BinaryPartScan & part_, const std::string & index_type = "BINARYMSTG",
+                   const std::string & params = "")
+        : part(part_)
+    {
+        mqvs_index_t h = nullptr;
+        check(mqvs_index_build(part.handle(), index_type.c_str(), params.c_str(), &h));
+        idx = std::make_shared<IndexHandle>(h, true);
+    }
+
+    /// A view of an index owned elsewhere (a PartCache entry).
+    static BinaryGpuIndex borrow(const BinaryPartScan & part, mqvs_index_t h) { return BinaryGpuIndex(part, h); }
+
+    mqvs_index_t handle() const { return idx->h; }
+    const BinaryPartScan & segment() const { return part; }
+    mqvs_index_t release() const
+    {
+        idx->owned = false;
+        return idx->h;
+    }
+
+    /// The CPU index search BinaryGpuIndex replaces, same arguments and outputs.
+    using SearchFallback = std::function<void(const uint8_t * queries, int32_t nq, int32_t k,
+                                              const std::string & params, const uint8_t * filter,
+                                              const uint8_t * row_exists, int64_t * ids, float * dist)>;
+
+    /// params: alpha / nprobe / metric (num_reorder is accepted and ignored).
+    /// fallback: runs instead when the device fails (isFallbackStatus).
+    void search(const uint8_t * queries, int32_t nq, int32_t query_bytes, int32_t k, const std::string & params,
+                const uint8_t * filter, const uint8_t * row_exists, int64_t * ids, float * dist,
+                const SearchFallback & fallback = nullptr) const
+    {
+        part.checkCodeBytes(query_bytes);
+        const int st = mqvs_index_search_binary(idx->h, queries, nq, k, params.c_str(), filter, row_exists, ids, dist,
+                                                0u, nullptr);
+        checkOrFallback(st, static_cast<bool>(fallback),
+                        [&] { fallback(queries, nq, k, params, filter, row_exists, ids, dist); });
+    }
+
+    /// VIWithMeta::row_ids_map of a decoupled part (source row -> new row);
+    /// an empty map clears it.
+    void setRowIdsMap(const std::vector<uint64_t> & row_ids_map) const
+    {
+        check(mqvs_index_set_row_ids_map(idx->h, row_ids_map.empty() ? nullptr : row_ids_map.data(),
+                                         static_cast<int64_t>(row_ids_map.size()), 0));
+    }
+
+private:
+    BinaryGpuIndex(const BinaryPartScan & part_, mqvs_index_t h)
+        : part(part_), idx(std::make_shared<IndexHandle>(h, false))
+    {
+    }
+
+    BinaryPartScan part;
+    std::shared_ptr<IndexHandle> idx;
+};
+
 /// getRealBitmap (VIUtils.cpp:479-497): a filter over the decoupled part's
 /// new_rows rows -> the filter over source part own_id's old_rows rows.
 inline std::vector<uint8_t> getRealBitmap(const std::vector<uint8_t> & new_filter, int64_t new_rows,

@@ -69,6 +69,11 @@ struct mqvs_index {
     size_t bytes = 0;
     double build_ms = 0.0;
     int np95 = 0;                  // nprobe measured to reach recall@10 0.95 on the build's sample (0: not measured)
+    // binary index (BINARYMSTG; kernels_bivf.hip): metric is Hamming or
+    // Jaccard, perm / list_off as above (no padding positions)
+    bool binary = false;
+    uint32_t *bplane = nullptr;    // [npos][code_words] codes in list order
+    uint32_t *bcent = nullptr;     // [nlist][code_words] k-majority centroids
 };
 
 namespace mqvs {
@@ -281,7 +286,7 @@ static void free_index(mqvs_index *ix) {
     if (ix->cent) segment_release(ix->cent);
     for (void *q : {(void *)ix->plane, (void *)ix->perm, (void *)ix->pnorm, (void *)ix->list_off, (void *)ix->cplane,
                     (void *)ix->cperm, (void *)ix->cpnorm, (void *)ix->clist_off, (void *)ix->row_ids_map,
-                    (void *)ix->yrec})
+                    (void *)ix->yrec, (void *)ix->bplane, (void *)ix->bcent})
         if (q) (void)hipFree(q);
     if (cur >= 0) (void)hipSetDevice(cur);
     delete ix;
@@ -322,13 +327,20 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
 static mqvs_index *build_auto(mqvs_segment *seg, const char *index_type, const char *params);
 constexpr int64_t kAutoNlistMinRows = 1 << 20;  // smaller parts take the default list count
 
+static mqvs_index *build_binary_impl(mqvs_segment *seg, const char *params);
+
 static mqvs_index *build_impl(mqvs_segment *seg, const char *index_type, const char *params) {
     if (!seg) fail(MQVS_ERR_BAD_ARGUMENTS, "null segment");
-    if (seg->binary) fail(MQVS_ERR_NOT_IMPLEMENTED, "vector index over binary vectors is not implemented");
-    std::string type = index_type ? index_type : "MSTG";
+    std::string type = index_type ? index_type : (seg->binary ? "BINARYMSTG" : "MSTG");
     for (auto &ch : type) ch = (char)std::toupper((unsigned char)ch);
-    if (type != "MSTG" && type != "IVFFLAT")
-        fail(MQVS_ERR_NOT_IMPLEMENTED, "index type `" + type + "` is not implemented (MSTG, IVFFLAT)");
+    const bool btype = type == "BINARYMSTG" || type == "BINARYIVF";
+    if (!btype && type != "MSTG" && type != "IVFFLAT")
+        fail(MQVS_ERR_NOT_IMPLEMENTED,
+             "index type `" + type + "` is not implemented (MSTG, IVFFLAT, BINARYMSTG, BINARYIVF)");
+    if (btype != seg->binary)
+        fail(MQVS_ERR_LOGICAL, "index type `" + type + "` does not match the segment's vectors (" +
+                                   (seg->binary ? "binary: BINARYMSTG, BINARYIVF" : "Float32: MSTG, IVFFLAT") + ")");
+    if (btype) return build_binary_impl(seg, params);
     const auto pm = parse_params(params);
     check_keys(pm, {"alpha", "metric_type", "nlist", "kmeans_iters", "sample"}, "index");
     int metric = seg->metric;
@@ -808,6 +820,7 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
                               uint32_t flags, hipStream_t user_stream, int formula_nq, int maxv_hint) {
     const int fnq = formula_nq > 0 ? formula_nq : nq;
     if (!ix) fail(MQVS_ERR_BAD_ARGUMENTS, "null index");
+    if (ix->binary) fail(MQVS_ERR_LOGICAL, "binary index: search it with mqvs_index_search_binary");
     if (nq < 0 || k < 0) fail(MQVS_ERR_BAD_ARGUMENTS, "nq and k must be non-negative");
     if (nq > 0 && k > 0 && (!queries || !out_ids || !out_dist))
         fail(MQVS_ERR_BAD_ARGUMENTS, "null query or output pointer");
@@ -1193,6 +1206,322 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
     g_istats = st;
 }
 
+// ---- binary index (BINARYMSTG seam) -------------------------------------------
+// The reference's index over FixedString(N) columns (KAT 00038); MSTG's code
+// is absent, so this is the library's own design: an inverted file over
+// k-majority (Hamming k-means) lists, kernels_bivf.hip.  Binary distances are
+// exact integers (Jaccard: one fp32 division of two integers), so the list
+// scan computes the final distance and the search has no approximate stage:
+// every returned distance equals mqvs_search_binary's on the same row, and a
+// search that probes every list equals mqvs_search_binary bit for bit.
+//
+// Build (deterministic: integer arithmetic only).  The coarse metric is
+// Hamming for both index metrics.  Sample rows floor(i n / S), initial
+// centroids sample rows floor(c S / L); per iteration every sample row goes
+// to the centroid at the smallest Hamming distance (ties: lowest list id) and
+// each centroid bit becomes the majority of its members (2 ones > members; a
+// list with no members keeps its centroid).  Every row is then assigned by
+// the same rule and the codes are copied grouped by list, ascending row
+// within a list.
+static int binary_metric_of(const std::string &name, const char *what) {
+    std::string mt = name;
+    for (auto &ch : mt) ch = (char)std::toupper((unsigned char)ch);
+    if (mt == "HAMMING") return MQVS_METRIC_HAMMING;
+    if (mt == "JACCARD") return MQVS_METRIC_JACCARD;
+    fail(MQVS_ERR_NOT_IMPLEMENTED, std::string(what) + " `" + name + "` is not supported for binary vectors");
+}
+
+static mqvs_index *build_binary_impl(mqvs_segment *seg, const char *params) {
+    const auto pm = parse_params(params);
+    check_keys(pm, {"alpha", "metric_type", "nlist", "kmeans_iters", "sample"}, "index");
+    const int metric = pm.count("metric_type") ? binary_metric_of(pm.at("metric_type"), "metric_type") : seg->metric;
+    const int64_t n = seg->n;
+    if (n >= ((int64_t)1 << 31)) fail(MQVS_ERR_NOT_IMPLEMENTED, "binary index over 2^31 or more rows");
+    const int cw = seg->code_words;
+    const int64_t dflt_nlist = std::max<int64_t>(1, std::min<int64_t>(65536, (n + 128) / 256));
+    const int64_t L = (int64_t)num_param(pm, "nlist", (double)dflt_nlist, 1, 1 << 20);
+    if (n > 0 && L > n) fail(MQVS_ERR_BAD_ARGUMENTS, "nlist must not exceed the number of rows");
+    const int iters = (int)num_param(pm, "kmeans_iters", 8, 0, 1000);
+    const int64_t dflt_sample = std::min<int64_t>(n, std::max<int64_t>(16 * L, std::min<int64_t>(64 * L, 1 << 20)));
+    const int64_t S = std::max<int64_t>(std::min<int64_t>(n, (int64_t)num_param(pm, "sample", (double)dflt_sample,
+                                                                                 1, 1e12)),
+                                        std::min<int64_t>(n, L));
+
+    DeviceGuard guard(seg->device);
+    hipStream_t s = thread_stream(seg->device);
+    hipEvent_t e0, e1;
+    MQVS_HIP(hipEventCreate(&e0));
+    MQVS_HIP(hipEventCreate(&e1));
+    MQVS_HIP(hipEventRecord(e0, s));
+    auto *ix = new mqvs_index();
+    try {
+        ix->seg = seg;
+        ix->binary = true;
+        ix->metric = metric;
+        ix->coarse_metric = MQVS_METRIC_HAMMING;
+        ix->nlist = L;
+        ix->alpha = (float)num_param(pm, "alpha", 3.0, 1.0, 4.0);
+        ix->bcent = dalloc<uint32_t>(ix, (size_t)L * cw);
+        MQVS_HIP(hipMemsetAsync(ix->bcent, 0, sizeof(uint32_t) * (size_t)L * cw, s));
+        TmpBuf assign(sizeof(int32_t) * std::max<int64_t>(n, 1));
+        if (S > 0) {
+            // ---- k-majority on a strided sample of the rows
+            std::vector<int32_t> sidx(S);
+            for (int64_t i = 0; i < S; ++i) sidx[i] = (int32_t)((__int128)i * n / S);
+            const int64_t Li = std::min(L, S);
+            std::vector<int32_t> init(Li);
+            for (int64_t c = 0; c < Li; ++c) init[c] = (int32_t)((__int128)c * S / Li);
+            TmpBuf didx(sizeof(int32_t) * S), dinit(sizeof(int32_t) * Li), samp(sizeof(uint32_t) * (size_t)S * cw);
+            MQVS_HIP(hipMemcpyAsync(didx.p, sidx.data(), sizeof(int32_t) * S, hipMemcpyHostToDevice, s));
+            MQVS_HIP(hipMemcpyAsync(dinit.p, init.data(), sizeof(int32_t) * Li, hipMemcpyHostToDevice, s));
+            launch_bivf_gather(seg->codes, cw, didx.as<int32_t>(), S, samp.as<uint32_t>(), s);
+            launch_bivf_gather(samp.as<uint32_t>(), cw, dinit.as<int32_t>(), Li, ix->bcent, s);
+            MQVS_HIP(hipGetLastError());
+            TmpBuf counts(sizeof(uint32_t) * (size_t)L * cw * 32), members(sizeof(uint32_t) * L);
+            for (int it = 0; it < iters; ++it) {
+                launch_bivf_assign(samp.as<uint32_t>(), S, cw, ix->bcent, (int)L, assign.as<int32_t>(), s);
+                MQVS_HIP(hipMemsetAsync(counts.p, 0, sizeof(uint32_t) * (size_t)L * cw * 32, s));
+                MQVS_HIP(hipMemsetAsync(members.p, 0, sizeof(uint32_t) * L, s));
+                launch_bivf_majority(samp.as<uint32_t>(), S, cw, assign.as<int32_t>(), (int)L, counts.as<uint32_t>(),
+                                     members.as<uint32_t>(), ix->bcent, s);
+                MQVS_HIP(hipGetLastError());
+            }
+            MQVS_HIP(hipStreamSynchronize(s));  // (sidx / init are host temporaries)
+        }
+        // ---- every row to its nearest centroid; lists in row order (a stable
+        // counting sort on the host)
+        std::vector<int32_t> ha(n);
+        if (n > 0) {
+            launch_bivf_assign(seg->codes, n, cw, ix->bcent, (int)L, assign.as<int32_t>(), s);
+            MQVS_HIP(hipGetLastError());
+            MQVS_HIP(hipMemcpyAsync(ha.data(), assign.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+            MQVS_HIP(hipStreamSynchronize(s));
+        }
+        std::vector<int64_t> off(L + 1, 0);
+        for (int64_t i = 0; i < n; ++i) {
+            if (ha[i] < 0 || ha[i] >= L) fail(MQVS_ERR_DEVICE, "binary index build: list id out of range");
+            ++off[ha[i] + 1];
+        }
+        for (int64_t l = 0; l < L; ++l) {
+            ix->max_list = std::max(ix->max_list, off[l + 1]);
+            off[l + 1] += off[l];
+        }
+        std::vector<int32_t> order(n);
+        {
+            std::vector<int64_t> cur(off.begin(), off.end() - 1);
+            for (int64_t i = 0; i < n; ++i) order[cur[ha[i]]++] = (int32_t)i;
+        }
+        ix->npos = n;
+        ix->rows_indexed = n;
+        ix->perm = dalloc<int32_t>(ix, n);
+        ix->list_off = dalloc<int64_t>(ix, L + 1);
+        ix->bplane = dalloc<uint32_t>(ix, (size_t)n * cw);
+        if (n > 0) MQVS_HIP(hipMemcpyAsync(ix->perm, order.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
+        MQVS_HIP(hipMemcpyAsync(ix->list_off, off.data(), sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, s));
+        launch_bivf_gather(seg->codes, cw, ix->perm, n, ix->bplane, s);
+        MQVS_HIP(hipGetLastError());
+        MQVS_HIP(hipEventRecord(e1, s));
+        MQVS_HIP(hipStreamSynchronize(s));
+        float ms = 0.f;
+        MQVS_HIP(hipEventElapsedTime(&ms, e0, e1));
+        ix->build_ms = ms;
+    } catch (...) {
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        free_index(ix);
+        throw;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return ix;
+}
+
+// Search: the nprobe nearest centroids by (Hamming, list id) (every list, with
+// no ranking, when nprobe == nlist), the probed lists scanned with the search
+// metric, filter ∩ row_exists and the b < nBit rule applied per position, and
+// the k best by (distance, part row) taken by the brute-force path's final
+// select (which keeps the smallest rows of a tie group at the k-th key however
+// large the group is).  probes_out (mqvs_index_probes_binary): the coarse
+// step's probes[nq][nprobe] are copied there and the search ends.
+static void search_binary_index_impl(mqvs_index *ix, const uint8_t *queries, int nq, int k, const char *params,
+                                     const uint8_t *filter, const uint8_t *exists, int64_t *out_ids, float *out_dist,
+                                     uint32_t flags, hipStream_t user_stream, int64_t *probes_out) {
+    if (!ix) fail(MQVS_ERR_BAD_ARGUMENTS, "null index");
+    if (!ix->binary) fail(MQVS_ERR_LOGICAL, "Float32 index: search it with mqvs_index_search");
+    if (nq < 0 || k < 0) fail(MQVS_ERR_BAD_ARGUMENTS, "nq and k must be non-negative");
+    if (nq > 0 && k > 0 && (!queries || !out_ids || !out_dist))
+        fail(MQVS_ERR_BAD_ARGUMENTS, "null query or output pointer");
+    if (k > kMaxK) fail(MQVS_ERR_BAD_ARGUMENTS, "k above " + std::to_string(kMaxK) + " not supported");
+    const auto pm = parse_params(params);
+    check_keys(pm, {"alpha", "nprobe", "num_reorder", "metric"}, "search");
+    const int metric = pm.count("metric") ? binary_metric_of(pm.at("metric"), "metric") : ix->metric;
+    const double alpha = num_param(pm, "alpha", ix->alpha, 1.0, 4.0);
+    const int nprobe = pm.count("nprobe")
+                           ? (int)num_param(pm, "nprobe", 1, 1, (double)std::min<int64_t>(ix->nlist, kSortCap))
+                           : nprobe_of(ix, alpha);
+    // (accepted and ignored: the scan is exact, nothing is re-ordered)
+    (void)num_param(pm, "num_reorder", 1, 1, (double)kLargeCap);
+    mqvs_index_search_stats st{};
+    st.nq = nq;
+    st.k = k;
+    st.nprobe = nprobe;
+    g_istats = st;
+    if (nq == 0 || k == 0) return;
+
+    mqvs_segment *seg = ix->seg;
+    const bool rank = nprobe < ix->nlist;
+    // a query's records: at most every position of its probed lists
+    const int64_t cap = std::max<int64_t>(1, std::min<int64_t>((int64_t)nprobe * ix->max_list, ix->npos));
+    {
+        // query sub-batches under the scratch budget (records, centroid
+        // distances, the large-k sort scratch)
+        const int64_t perq = cap * (int64_t)sizeof(Cand) + (rank ? ix->nlist * 4 : 0) +
+                             (k > kSortCap ? (int64_t)sizeof(uint4) * 2 * kLargeCap : 0);
+        const int qb = (int)std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)scratch_budget() / perq));
+        if (nq > qb) {
+            mqvs_index_search_stats sum{};
+            for (int q0 = 0; q0 < nq; q0 += qb) {
+                const int m = std::min(qb, nq - q0);
+                search_binary_index_impl(ix, queries + (size_t)q0 * seg->code_bytes, m, k, params, filter, exists,
+                                         out_ids + (size_t)q0 * k, out_dist + (size_t)q0 * k, flags, user_stream,
+                                         probes_out ? probes_out + (size_t)q0 * nprobe : nullptr);
+                sum.coarse_ms += g_istats.coarse_ms;
+                sum.scan_ms += g_istats.scan_ms;
+                sum.select_ms += g_istats.select_ms;
+                sum.total_ms += g_istats.total_ms;
+                sum.values += g_istats.values;
+                sum.items += g_istats.items;
+                sum.plane_bytes += g_istats.plane_bytes;
+                sum.pairs += g_istats.pairs;
+            }
+            sum.nq = nq;
+            sum.k = k;
+            sum.nprobe = nprobe;
+            g_istats = sum;
+            return;
+        }
+    }
+
+    DeviceGuard guard(seg->device);
+    IndexWorkspace &ws = index_workspace(seg->device);
+    WsScope scope(seg->device, &ws);
+    hipStream_t s = user_stream ? user_stream : thread_stream(seg->device);
+    scope.set_stream(s);
+    const bool dev = flags & MQVS_F_DEVICE_PTRS;
+    const bool tev = timing_on(flags);
+    const int cw = seg->code_words;
+    if (tev) MQVS_HIP(hipEventRecord(ws.ev[0], s));
+
+    // queries -> zero-padded [nq][code_words]
+    auto *qc = (uint32_t *)ws.queries.get(sizeof(uint32_t) * (size_t)nq * cw);
+    MQVS_HIP(hipMemsetAsync(qc, 0, sizeof(uint32_t) * (size_t)nq * cw, s));
+    MQVS_HIP(hipMemcpy2DAsync(qc, (size_t)cw * 4, queries, (size_t)seg->code_bytes, (size_t)seg->code_bytes, (size_t)nq,
+                              dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    const uint8_t *dfilter = filter, *dexists = exists;
+    const int64_t bm = (seg->n + 7) / 8;
+    int64_t *dids = out_ids;
+    float *ddist = out_dist;
+    if (!dev) {
+        if (filter) {
+            auto *f = (uint8_t *)ws.filter.get(bm);
+            stage_in(ws.pin_f, f, filter, bm, s);
+            dfilter = f;
+        }
+        if (exists) {
+            auto *f = (uint8_t *)ws.exists.get(bm);
+            stage_in(ws.pin_e, f, exists, bm, s);
+            dexists = f;
+        }
+        dids = (int64_t *)ws.out_ids.get(sizeof(int64_t) * (size_t)nq * k);
+        ddist = (float *)ws.out_dist.get(sizeof(float) * (size_t)nq * k);
+    }
+    // [0] the final select's overflow word (never set: a region holds every
+    // position of its lists)
+    int *status = (int *)ws.status.get(sizeof(int) * 8);
+    int *count = (int *)ws.fine.lcount.get(sizeof(int) * nq);
+    launch_fill2(reinterpret_cast<uint32_t *>(status), 8, 0u, reinterpret_cast<uint32_t *>(count), nq, 0u, s);
+
+    // ---- coarse
+    int64_t *probes = (int64_t *)ws.probes.get(sizeof(int64_t) * (size_t)nq * nprobe);
+    if (rank) {
+        auto *cd = (uint32_t *)ws.pdist.get(sizeof(uint32_t) * (size_t)nq * ix->nlist);
+        launch_bivf_coarse(ix->bcent, (int)ix->nlist, cw, qc, nq, nprobe, cd, probes, s);
+    } else {
+        launch_iota_probes(probes, nq, nprobe, s);
+    }
+    MQVS_HIP(hipGetLastError());
+    if (tev) {
+        MQVS_HIP(hipEventRecord(ws.ev[1], s));
+        MQVS_HIP(hipEventRecord(ws.ev[2], s));
+    }
+    if (probes_out) {
+        MQVS_HIP(hipMemcpyAsync(probes_out, probes, sizeof(int64_t) * (size_t)nq * nprobe, hipMemcpyDeviceToHost, s));
+        MQVS_HIP(hipEventRecord(ws.ev[5], s));
+        host_wait(s);
+        return;
+    }
+
+    // ---- the probed lists
+    BivfParams p{};
+    p.plane = ix->bplane;
+    p.perm = ix->perm;
+    p.list_off = ix->list_off;
+    p.nlist = (int)ix->nlist;
+    p.code_words = cw;
+    p.nbits = seg->d;
+    p.nq = nq;
+    p.nprobe = nprobe;
+    p.nch = (int)((ix->max_list + 255) / 256);
+    p.probes = probes;
+    p.qcodes = qc;
+    p.filter = dfilter;
+    p.exists = dexists;
+    p.cand = (Cand *)ws.fine.cand.get(sizeof(Cand) * (size_t)nq * cap);
+    p.cand_count = count;
+    p.cand_cap = (int)cap;
+    int64_t *dstats = (int64_t *)ws.fine.stats.get(sizeof(int64_t) * 4);
+    launch_bivf_scan(p, metric, dstats, s);
+    MQVS_HIP(hipGetLastError());
+    if (tev) MQVS_HIP(hipEventRecord(ws.ev[3], s));
+    uint4 *large = k > kSortCap ? (uint4 *)ws.fine.large.get(sizeof(uint4) * 2 * kLargeCap * (size_t)nq) : nullptr;
+    // ascending finite values: the L2 ordering key, (key, row) ties
+    launch_final_select(p.cand, count, (int)cap, nq, k, MQVS_METRIC_L2, 0, seg->row_offset, dids, ddist, status, large,
+                        s);
+    MQVS_HIP(hipGetLastError());
+    if (tev) MQVS_HIP(hipEventRecord(ws.ev[4], s));
+    MQVS_HIP(hipEventRecord(ws.ev[5], s));
+
+    // decoupled part: results in the new part's row ids
+    if (ix->row_ids_map) launch_map_ids(dids, (int64_t)nq * k, ix->row_ids_map, s);
+    if (dev && (flags & MQVS_F_ASYNC)) {
+        launch_async_flags(status, nullptr, 0, async_sticky(seg->device, s), s);
+        MQVS_HIP(hipGetLastError());
+        return;
+    }
+    int64_t *hs = ws.host;
+    int *hst = reinterpret_cast<int *>(ws.host + 4);
+    if (!dev) stage_out_begin(ws.pin_o, dids, ddist, (size_t)nq * k, s);
+    launch_words_to_host(dstats, 4, status, 8, hs, hst, s);
+    MQVS_HIP(hipGetLastError());
+    host_wait(s);
+    if (*hst) fail(MQVS_ERR_DEVICE, "binary index search: a query's record region overflowed");
+    if (!dev) stage_out_end(ws.pin_o, out_ids, out_dist, (size_t)nq * k);
+    st.values = hs[0];
+    st.items = hs[1];
+    st.plane_bytes = hs[2];
+    st.pairs = hs[3];
+    if (tev) {
+        float t[4] = {0, 0, 0, 0}, tot = 0;
+        for (int i = 0; i < 4; ++i) MQVS_HIP(hipEventElapsedTime(&t[i], ws.ev[i], ws.ev[i + 1]));
+        MQVS_HIP(hipEventElapsedTime(&tot, ws.ev[0], ws.ev[5]));
+        st.coarse_ms = t[0];
+        st.scan_ms = t[2];
+        st.select_ms = t[3];
+        st.total_ms = tot;
+    }
+    g_istats = st;
+}
+
 }  // namespace mqvs
 
 using namespace mqvs;
@@ -1240,6 +1569,7 @@ int mqvs_index_search(mqvs_index_t idx, const float *queries, int32_t nq, int32_
 int mqvs_index_centroids(mqvs_index_t idx, float *out, int64_t cap) {
     return guarded([&] {
         if (!idx || !out) fail(MQVS_ERR_BAD_ARGUMENTS, "null argument");
+        if (idx->binary) fail(MQVS_ERR_LOGICAL, "binary index: read its centroids with mqvs_index_centroids_binary");
         if (!idx->cent) fail(MQVS_ERR_LOGICAL, "index has no centroid table");
         const int64_t need = idx->cent->n * (int64_t)idx->cent->d;
         if (cap < need) fail(MQVS_ERR_BAD_ARGUMENTS, "output holds " + std::to_string(cap) + " floats, " +
@@ -1263,6 +1593,47 @@ int mqvs_index_probes(mqvs_index_t idx, const float *queries, int32_t nq, const 
         std::vector<int64_t> ids((size_t)nq);
         std::vector<float> dd((size_t)nq);
         search_index_impl(idx, queries, nq, 1, params, nullptr, nullptr, ids.data(), dd.data(), 0, nullptr, 0);
+    });
+}
+
+int mqvs_index_search_binary(mqvs_index_t idx, const uint8_t *queries, int32_t nq, int32_t k, const char *params,
+                             const uint8_t *filter, const uint8_t *row_exists, int64_t *out_ids, float *out_dist,
+                             uint32_t flags, mqvs_stream_t stream) {
+    return guarded([&] {
+        fault_point();
+        WaitScope wsc{6, (uint64_t)(uintptr_t)idx, (uint64_t)nq, (uint64_t)k, wait_str_hash(params), filter != nullptr,
+                      row_exists != nullptr, flags};
+        search_binary_index_impl(idx, queries, nq, k, params, filter, row_exists, out_ids, out_dist, flags,
+                                 (hipStream_t)stream, nullptr);
+    });
+}
+
+int mqvs_index_centroids_binary(mqvs_index_t idx, uint8_t *out, int64_t cap_bytes) {
+    return guarded([&] {
+        if (!idx || !out) fail(MQVS_ERR_BAD_ARGUMENTS, "null argument");
+        if (!idx->binary) fail(MQVS_ERR_LOGICAL, "Float32 index: read its centroids with mqvs_index_centroids");
+        const int64_t nb = idx->seg->code_bytes;
+        const int64_t need = idx->nlist * nb;
+        if (cap_bytes < need) fail(MQVS_ERR_BAD_ARGUMENTS, "output holds " + std::to_string(cap_bytes) + " bytes, " +
+                                                               std::to_string(need) + " needed");
+        DeviceGuard guard(idx->seg->device);
+        MQVS_HIP(hipMemcpy2D(out, (size_t)nb, idx->bcent, (size_t)idx->seg->code_words * 4, (size_t)nb,
+                             (size_t)idx->nlist, hipMemcpyDeviceToHost));
+    });
+}
+
+int mqvs_index_probes_binary(mqvs_index_t idx, const uint8_t *queries, int32_t nq, const char *params,
+                             int64_t *out_probes) {
+    return guarded([&] {
+        if (!idx || (nq > 0 && (!queries || !out_probes))) fail(MQVS_ERR_BAD_ARGUMENTS, "null argument");
+        if (nq < 0) fail(MQVS_ERR_BAD_ARGUMENTS, "nq must be non-negative");
+        if (nq == 0) return;
+        WaitScope wsc{7, (uint64_t)(uintptr_t)idx, (uint64_t)nq, wait_str_hash(params)};
+        // k 1: the coarse step does not depend on k; the search stops after it
+        std::vector<int64_t> ids((size_t)nq);
+        std::vector<float> dd((size_t)nq);
+        search_binary_index_impl(idx, queries, nq, 1, params, nullptr, nullptr, ids.data(), dd.data(), 0, nullptr,
+                                 out_probes);
     });
 }
 

@@ -528,6 +528,38 @@ void launch_centroid_mean(const float *rows, int d, const int32_t *order, const 
                           hipStream_t s);
 
 // ---------------------------------------------------------------------------
+// Binary index path (kernels_bivf.hip, index.hip)
+struct BivfParams {
+    const uint32_t *plane;    // [npos][code_words] codes in list order
+    const int32_t *perm;      // [npos] part row of each position
+    const int64_t *list_off;  // [nlist+1] list start positions
+    int nlist;
+    int code_words;
+    int nbits;                // Hamming distances == nbits are never returned
+    int nq, nprobe;
+    int nch;                  // 256-position slices per (query, probed list): ceil(longest list / 256)
+    const int64_t *probes;    // [nq][nprobe] list ids
+    const uint32_t *qcodes;   // [nq][code_words]
+    const uint8_t *filter;    // PREWHERE bitmap (rows) or null
+    const uint8_t *exists;    // LWD bitmap (rows) or null
+    Cand *cand;               // [nq][cand_cap] (distance, part row) of the kept positions
+    int *cand_count;          // [nq]
+    int cand_cap;
+};
+void launch_bivf_assign(const uint32_t *codes, int64_t n, int code_words, const uint32_t *cent, int nlist,
+                        int32_t *assign, hipStream_t s);
+// counts [nlist][code_words][32] and members [nlist] must be zero
+void launch_bivf_majority(const uint32_t *codes, int64_t m, int code_words, const int32_t *assign, int nlist,
+                          uint32_t *counts, uint32_t *members, uint32_t *cent, hipStream_t s);
+void launch_bivf_gather(const uint32_t *src, int code_words, const int32_t *idx, int64_t m, uint32_t *dst,
+                        hipStream_t s);
+// cdist: [nq][nlist] words of scratch; nprobe < nlist
+void launch_bivf_coarse(const uint32_t *cent, int nlist, int code_words, const uint32_t *qcodes, int nq, int nprobe,
+                        uint32_t *cdist, int64_t *probes, hipStream_t s);
+// metric: Hamming or Jaccard; stats (optional): [4] values, items, plane bytes, pairs
+void launch_bivf_scan(const BivfParams &p, int metric, int64_t *stats, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // Error plumbing
 void set_error(const std::string &msg);
 

@@ -24,7 +24,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import F_ASYNC, F_DEVICE_PTRS, F_FIRST_STAGE, F_RERANK_ALL, check, lib
-from .vector_scan import VectorScanSegment, _host_f32, _host_u8, _is_torch, _ptr
+from .vector_scan import BinaryVectorScanSegment, VectorScanSegment, _host_f32, _host_u8, _is_torch, _ptr
 
 
 def _params(p) -> bytes:
@@ -132,6 +132,89 @@ class VectorIndex:
         if self._h:
             check(lib.mqvs_index_free(self._h))
             self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class BinaryVectorIndex:
+    """A BINARYMSTG-type index over a resident BinaryVectorScanSegment (the
+    segment must outlive it): an inverted file over k-majority lists, exact
+    Hamming / Jaccard distances (mqvs_index_search_binary, include/mqvs.h)."""
+
+    def __init__(self, handle, segment: BinaryVectorScanSegment):
+        self._h = handle
+        self.segment = segment
+
+    @classmethod
+    def build(cls, segment: BinaryVectorScanSegment, index_type="BINARYMSTG", params=None):
+        h = ctypes.c_void_p()
+        check(lib.mqvs_index_build(segment._h, index_type.encode(), _params(params), ctypes.byref(h)))
+        return cls(h, segment)
+
+    set_row_ids_map = VectorIndex.set_row_ids_map
+    info = VectorIndex.info
+
+    def _host_queries(self, queries):
+        q = _host_u8(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.segment.nbytes:
+            raise _lib.MqvsError(_lib.ERR_LOGICAL,
+                                 f"query length {q.shape[1]} bytes != column FixedString({self.segment.nbytes})")
+        return q
+
+    def centroids(self):
+        """The coarse step's centroid table, uint8[nlist, N]."""
+        c = np.empty((self.info()["nlist"], self.segment.nbytes), np.uint8)
+        check(lib.mqvs_index_centroids_binary(self._h, _ptr(c), c.size))
+        return c
+
+    def probes(self, queries, params=None):
+        """The lists a search with `params` probes, int64[nq, nprobe] (no order)."""
+        q = self._host_queries(queries)
+        nq = q.shape[0]
+        buf = np.full((nq, self.info()["nlist"]), -1, np.int64)
+        check(lib.mqvs_index_probes_binary(self._h, _ptr(q), nq, _params(params), _ptr(buf)))
+        npb = _lib.last_index_stats()["nprobe"]
+        return buf.reshape(-1)[: nq * npb].reshape(nq, npb).copy()
+
+    def search(self, queries, k, params=None, filter_bitmap=None, row_exists=None, first_stage_only=False,
+               out=None, async_=False, stream=None):
+        """(ids[nq,k] int64, dist[nq,k] float32) as BinaryVectorScanSegment.search:
+        ascending by (distance, row), -1 / FLT_MAX padded.  The distances are
+        exact, so first_stage_only returns the same result."""
+        fs = F_FIRST_STAGE if first_stage_only else 0
+        pr = _params(params)
+        if _is_torch(queries):
+            import torch
+            assert queries.is_cuda and queries.is_contiguous() and queries.dtype == torch.uint8
+            nq = queries.shape[0]
+            if queries.shape[1] != self.segment.nbytes:
+                raise _lib.MqvsError(_lib.ERR_LOGICAL, f"query length {queries.shape[1]} bytes != column "
+                                                       f"FixedString({self.segment.nbytes})")
+            if out is None:
+                ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
+                dist = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
+            else:
+                ids, dist = out
+            flags = F_DEVICE_PTRS | (F_ASYNC if async_ else 0) | fs
+            check(lib.mqvs_index_search_binary(self._h, _ptr(queries), nq, k, pr, _ptr(filter_bitmap),
+                                               _ptr(row_exists), _ptr(ids), _ptr(dist), flags,
+                                               ctypes.c_void_p(stream) if stream else None))
+            return ids, dist
+        q = self._host_queries(queries)
+        nq = q.shape[0]
+        ids = np.empty((nq, k), np.int64)
+        dist = np.empty((nq, k), np.float32)
+        check(lib.mqvs_index_search_binary(self._h, _ptr(q), nq, k, pr, _ptr(_host_u8(filter_bitmap)),
+                                           _ptr(_host_u8(row_exists)), _ptr(ids), _ptr(dist), fs, None))
+        return ids, dist
+
+    free = VectorIndex.free
 
     def __del__(self):
         try:
