@@ -357,7 +357,14 @@ int mqvs_generate_device(uint64_t seed, int32_t mode, int64_t row0, int64_t n, i
  *   nlist        lists (default about n / 256, at most 65536)
  *   kmeans_iters k-means iterations (default 8)
  *   sample       k-means training rows (default min(n, max(16 nlist, min(64 nlist, 2^20))))
- * Unknown keys fail with MQVS_ERR_BAD_ARGUMENTS. */
+ * Unknown keys fail with MQVS_ERR_BAD_ARGUMENTS.
+ * Width limit: the list scan keeps a tile of 16, 32 or 64 bf16 queries in LDS,
+ * 16 QB (2 dpad + 16) + 256 QB bytes for 16 QB queries (dpad: the dimension
+ * rounded up to 64), and uses the largest tile that fits the device's
+ * per-workgroup LDS.  With the 160 KiB of an MI355X workgroup 64-query tiles
+ * serve dpad <= 1216, 32-query tiles dpad <= 2496 and 16-query tiles
+ * dpad <= 5056; a segment of more dimensions than that (5056 there) is
+ * refused with MQVS_ERR_BAD_ARGUMENTS and a message naming the limit. */
 typedef struct mqvs_index *mqvs_index_t;
 int mqvs_index_build(mqvs_segment_t seg, const char *index_type, const char *params, mqvs_index_t *out);
 int mqvs_index_free(mqvs_index_t idx);

@@ -360,6 +360,18 @@ static mqvs_index *build_impl(mqvs_segment *seg, const char *index_type, const c
     }
     const int64_t n = seg->n;
     const int d = seg->d;
+    {
+        // the list scan keeps a tile of at least 16 bf16 queries in LDS
+        // (ivf_scan_lds): rows too wide for that cannot be searched
+        DeviceGuard guard(seg->device);
+        const int64_t lim = device_lds_bytes();
+        if (ivf_fit_qg(16, rup(d, kBfK), lim) == 0) {
+            int64_t dmax = (lim / 16 - 32) / 2 / kBfK * kBfK;
+            fail(MQVS_ERR_BAD_ARGUMENTS, "dimension " + std::to_string(d) + " is too wide for an index: the list scan's " +
+                                             "16-query tile must fit the workgroup's " + std::to_string(lim) +
+                                             " bytes of LDS (at most " + std::to_string(dmax) + " dimensions)");
+        }
+    }
     if (!pm.count("nlist") && n >= kAutoNlistMinRows && !seg->nonempty_bits) return build_auto(seg, index_type, params);
     // lists of about 256 rows (at most 65536 lists): fine enough that data of
     // many small clusters (generator mode 3: 65536 centres of ~150 rows)
@@ -734,6 +746,13 @@ static int64_t *list_pass(ListBufs &b, const uint16_t *plane, const int32_t *per
         const int v = std::atoi(e);
         if (!dense && (v == 16 || v == 32 || v == 64)) p.qg = v;
     }
+    // wide rows: the largest of that size and its smaller siblings whose query
+    // tile fits a workgroup's LDS (64 up to dpad 1216, 32 up to 2496, 16 up to
+    // 5056 with 160 KiB; the dense plan groups by whatever p.qg is).  The
+    // build refuses wider rows, so something fits.
+    p.qg = ivf_fit_qg(p.qg, dpad, device_lds_bytes());
+    // (p.qg sizes the work items below; the build's own check keeps this from happening)
+    if (p.qg == 0) fail(MQVS_ERR_LOGICAL, "list scan: no query tile fits the workgroup's LDS");
     // work items = sum over probed lists of groups x 512-position slices
     // list positions per work item (a multiple of 64): 8 x the item's queries,
     // so the query tile stays a fixed share of the bytes an item reads (round

@@ -1127,6 +1127,11 @@ void launch_ivf_plan(const IvfParams &p, hipStream_t s) {
 template <int QB, bool NTL>
 static void ivf_scan_t(const IvfParams &p, int metric, int grid, hipStream_t s) {
     const size_t lds = (size_t)16 * QB * (2 * p.dpad + 16);
+    // (the caller sizes p.qg with ivf_fit_qg; a tile that does not fit is
+    // refused here, never launched)
+    if (ivf_scan_lds(16 * QB, p.dpad) > device_lds_bytes())
+        fail(MQVS_ERR_LOGICAL, "ivf scan: " + std::to_string(16 * QB) + "-query tile of " + std::to_string(p.dpad) +
+                                   " padded dimensions exceeds the workgroup's LDS");
     if (lds > 65536) {  // 64-query tiles of wide rows: opt in to more than 64 KiB of LDS
         MQVS_HIP(hipFuncSetAttribute((const void *)k_ivf_scan<MQVS_METRIC_L2, QB, NTL>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

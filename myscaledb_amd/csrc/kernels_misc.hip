@@ -402,19 +402,18 @@ __global__ __launch_bounds__(64) void k_query_prep(const float *q, int nq, int d
 }
 
 // generic d: elements in LDS, lane 0 walks the sequential sums
-// (phase 1 does everything here, phase 2 nothing)
+// (phase 1 makes the whole chain here; phase 2 -- launched after it, with the
+// qdelta buffer the re-rank's bound pruning reads -- only measures the spread
+// of the variants phase 1 stored)
 __global__ __launch_bounds__(64) void k_query_prep_lds(const float *q, int nq, int d, int metric, int blas,
                                                        float *qvars, int maxv, float *qnorms, int *qmu, int *qlam,
                                                        int *status, int phase, float *qdelta) {
-    if (phase == 2) return;
     extern __shared__ __attribute__((aligned(16))) float qbuf[];
     const int j = blockIdx.x;
     const int lane = threadIdx.x;
     const int64_t qs = (int64_t)((d + 31) / 32 * 32);
     const float *src = q + (int64_t)j * d;
     float *v0 = qvars + (int64_t)j * maxv * qs;
-    for (int i = lane; i < d; i += 64) qbuf[i] = src[i];
-    __syncthreads();
     // qdelta as k_query_prep's, from the stored variants [1, nv)
     auto put_delta = [&](int nv) {
         if (!qdelta) return;
@@ -430,6 +429,19 @@ __global__ __launch_bounds__(64) void k_query_prep_lds(const float *q, int nq, i
         for (int off = 32; off > 0; off >>= 1) dl += __shfl_xor(dl, off);
         if (lane == 0) qdelta[j] = (float)(sqrt(dl) * (1.0 + 1e-6)) + 1e-30f;
     };
+    if (phase == 2) {
+        // the stored variants are [0, mu + lambda) (all maxv when the chain
+        // did not repeat: phase 1 then left mu = maxv - 1, lambda = 1)
+        if (metric == MQVS_METRIC_COSINE) {
+            const int mu = qmu[j], lam = qlam[j];
+            put_delta((lam >= 1 && mu >= 0 && mu + lam <= maxv) ? mu + lam : maxv);
+        } else if (qdelta && lane == 0) {
+            qdelta[j] = 0.0f;
+        }
+        return;
+    }
+    for (int i = lane; i < d; i += 64) qbuf[i] = src[i];
+    __syncthreads();
     auto seqsum = [&]() -> float {
         if (lane == 0) {
             float s = 0.0f;

@@ -435,6 +435,18 @@ int device_cus() {
     return cus;
 }
 
+int64_t device_lds_bytes() {
+    static std::atomic<int> cache[64];
+    int dev = 0;
+    MQVS_HIP(hipGetDevice(&dev));
+    int lds = (dev >= 0 && dev < 64) ? cache[dev].load(std::memory_order_relaxed) : 0;
+    if (lds <= 0) {
+        MQVS_HIP(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        if (dev >= 0 && dev < 64) cache[dev].store(lds, std::memory_order_relaxed);
+    }
+    return lds;
+}
+
 int wait_spin_us() {
     const int m = g_wait_mode.load(std::memory_order_relaxed);
     return m == MQVS_WAIT_RUNTIME ? -1 : m == MQVS_WAIT_BLOCK ? 0 : g_wait_spin_us.load(std::memory_order_relaxed);

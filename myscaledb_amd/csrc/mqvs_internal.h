@@ -489,6 +489,18 @@ struct IvfRegions {
     int64_t *stats = nullptr;  // pair mode: [nq][4] values, items, plane bytes, pairs per query
 };
 
+// LDS of one k_ivf_scan workgroup with qg-query work items: the query tile
+// (qg rows of 2 dpad + 16 B, dynamic) + 16 B of pair records per query (static)
+inline int64_t ivf_scan_lds(int qg, int64_t dpad) { return (int64_t)qg * (2 * dpad + 16) + 16 * (int64_t)qg; }
+// The largest of `want` (64, 32 or 16) and its smaller siblings whose tile fits
+// lds_limit bytes; 0: not even 16 queries fit (no list scan at this width).
+// With the 160 KiB of a gfx950 workgroup: 64 up to dpad 1216, 32 up to 2496,
+// 16 up to 5056.
+inline int ivf_fit_qg(int want, int64_t dpad, int64_t lds_limit) {
+    for (int qg = want; qg >= 16; qg >>= 1)
+        if (ivf_scan_lds(qg, dpad) <= lds_limit) return qg;
+    return 0;
+}
 void launch_ivf_plan(const IvfParams &p, hipStream_t s);
 void launch_iota_probes(int64_t *probes, int nq, int np, hipStream_t s);
 void launch_ivf_plan_dense(const IvfParams &p, int64_t npos, hipStream_t s);
@@ -710,6 +722,9 @@ hipStream_t thread_stream(int device);
 // compute units of the current device (cached per device: launchers size
 // their persistent grids from it on every call)
 int device_cus();
+// LDS bytes one workgroup of the current device can have, static + dynamic
+// (hipDeviceAttributeMaxSharedMemoryPerBlock, read once per device)
+int64_t device_lds_bytes();
 // The host's wait for the work queued on `s` (every synchronous call ends with
 // one): the policy of mqvs_set_wait_mode -- the runtime's own
 // hipStreamSynchronize, or a short poll of a blocking-sync event's completion
