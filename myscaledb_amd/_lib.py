@@ -11,8 +11,9 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # The release library; nothing in the environment selects another one.  The
-# measurement build (libmqvs_dbg.so, `make dbg`: kernels that read A/B switches
-# from the environment) is loaded only by a tool that calls
+# measurement build (libmqvs_dbg.so, `make dbg`: the same kernels, with the
+# path switches of csrc/tuning.h read from the environment) is loaded only by a
+# tool that calls
 # use_measurement_build() explicitly, before its first library call.
 LIB_PATH = os.path.join(_HERE, "libmqvs.so")
 DBG_LIB_PATH = os.path.join(_HERE, "libmqvs_dbg.so")
@@ -210,9 +211,10 @@ lib = _Lib(_load(), LIB_PATH)
 
 def use_measurement_build():
     """For measurement tools only (tools/ab_split.py --dbg and the like): route
-    every later call of this process to libmqvs_dbg.so, whose kernels read A/B
-    switches (some of them diagnostic builds with wrong results) from the
-    environment.  The product path and the tests never call this."""
+    every later call of this process to libmqvs_dbg.so, which holds the
+    release library's kernels and reads the path switches listed in
+    csrc/tuning.h from the environment.  The product path and the tests never
+    call this."""
     lib._cdll, lib.path = _load(DBG_LIB_PATH), DBG_LIB_PATH
 
 

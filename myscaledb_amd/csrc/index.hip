@@ -113,7 +113,7 @@ struct IndexWorkspace final : WsExt {
     int64_t *host = nullptr;  // pinned: the search's stats [4] and status word (one sync, no staging copies)
     HostBuf pin_q, pin_f, pin_e, pin_o;  // pinned staging of host-pointer searches
     GBuf queries, qvars, qnorms, qmu, qlam, status, qhi, probes, cprobes, filter, exists, rows, out_ids, out_dist,
-        ord, dmap, dwords, pdist, cqhi, gmax, crec, cbq, craw, ibq, rsurv, rcnt, rrecs, qdelta, pstats;
+        ord, dmap, dwords, pdist, cqhi, gmax, crec, cbq, craw, ibq, qdelta, pstats;
     ListBufs coarse, fine;
     // WsExt: the owner is between calls (its workspace's `done` event passed:
     // the main stream, which joins the side chain, has drained)
@@ -123,7 +123,7 @@ struct IndexWorkspace final : WsExt {
         for (HostBuf *x : {&pin_q, &pin_f, &pin_e, &pin_o}) x->release();  // (host memory: not counted)
         for (GBuf *x : {&queries, &qvars, &qnorms, &qmu, &qlam, &status, &qhi, &probes, &cprobes, &filter, &exists,
                         &rows, &out_ids, &out_dist, &ord, &dmap, &dwords, &pdist, &cqhi, &gmax, &crec, &cbq, &craw,
-                        &ibq, &rsurv, &rcnt, &rrecs, &qdelta, &pstats}) {
+                        &ibq, &qdelta, &pstats}) {
             b += x->cap;
             x->release();
         }
@@ -967,9 +967,7 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
     // The chain starts after the coarse step: beside the coarse batch kernel
     // it slowed that kernel by ~20 us, beside the plan and the list scan it
     // costs less (mode 3, nprobe 1: 0.564 -> 0.544 ms per batch,
-    // profiles/r04/index/fork_ab.jsonl).  MQVS_IVF_FORK=0 (measurement build):
-    // start it right after variant 0.
-    const bool late_fork = tune_int("MQVS_IVF_FORK", 1) == 1;
+    // profiles/r04/index/fork_ab.jsonl).
     float *qdelta = nullptr;  // cosine, pruned re-rank: the chain's variant spread (k_query_prep phase 2)
     auto fork_chain = [&]() {
         MQVS_HIP(hipEventRecord(ws.fork, s));
@@ -980,7 +978,6 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
         MQVS_HIP(hipGetLastError());
         MQVS_HIP(hipEventRecord(ws.join, ws.side));
     };
-    if (split && !late_fork) fork_chain();
     uint16_t *qhi = (uint16_t *)ws.qhi.get(sizeof(uint16_t) * (size_t)nq * ix->dpad);
     launch_to_bf16(qvars, nq, d, (int64_t)maxv * qstride, qhi, ix->dpad, s);
     MQVS_HIP(hipGetLastError());
@@ -1002,14 +999,11 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
     // launch and one pick instead of mqvs_search's whole pipeline.
     bool picked = false;
     const int cmode = tune_int("MQVS_IVF_COARSE", 2);
-    // core groups of the pick: nprobe (any T keeps the probes exact; nprobe
-    // + 2 before: the core's 8 (nprobe + 2) centroids scored exactly, vs 8
-    // nprobe now -- mode 3 nprobe 1: 0.505 -> 0.499 ms per batch,
+    // (core groups of the pick: nprobe; any count keeps the probes exact,
+    // and more of them only score more centroids exactly,
     // profiles/r05/pick/core_t_ab.jsonl)
-    const int pick_t = std::max(1, nprobe + tune_int("MQVS_PICK_TX", 0));
     float *qrec0 = nullptr;  // variant 0's norm records (the pick's bound; the re-rank pruning's)
-    if (cmode == 2 && pick_t <= kCoarsePickMaxT && nprobe <= kCoarsePickMaxT && ix->cent && ix->cent->rows_hi &&
-        ix->cent->rows) {
+    if (cmode == 2 && nprobe <= kCoarsePickMaxT && ix->cent && ix->cent->rows_hi && ix->cent->rows) {
         mqvs_segment *cs = ix->cent;
         const int64_t vpad = rup(nq, 16);
         auto *cq = (uint16_t *)ws.cqhi.get(sizeof(uint16_t) * (size_t)vpad * cs->dpad);
@@ -1038,13 +1032,11 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
         cp.tile_rows = 256;
         cp.tiles = (cs->n + 255) / 256;
         cp.tiles_per_chunk = 0;
-        // groups of 8 centroids (round 5; 16 before): the pick scores half the
-        // centroids per group it takes
-        const int grp = tune_int("MQVS_IVF_GRP", 8) == 16 ? 16 : 8;
-        const int64_t gld = rup((256 / grp) * cp.tiles, 4);
+        // groups of 8 centroids: 32 per 256-row tile
+        const int64_t gld = rup(32 * cp.tiles, 4);
         cp.p4_gmax = (float *)ws.gmax.get(sizeof(float) * (size_t)nq * gld);
         cp.p4_gld = gld;
-        if (launch_scan_p4_groups(cp, ix->coarse_metric, grp, s)) {
+        if (launch_scan_p4_groups(cp, ix->coarse_metric, s)) {
             MQVS_HIP(hipGetLastError());
             // each query's bound on |bf16 group value - exact| (the direct
             // formula's rounding terms: the larger of the two)
@@ -1053,9 +1045,9 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
             bp.blas_nq = 1;
             launch_query_bound(bp, ix->coarse_metric, cs->ynorm_max, crec, cs->ynorm_max + 4, cbq, s);
             MQVS_HIP(hipGetLastError());
-            launch_coarse_pick(cp.p4_gmax, gld, (256 / grp) * cp.tiles, pick_t, nprobe, ix->coarse_metric, qvars,
-                               (int64_t)maxv * qstride, cs->rows, cs->norms, cs->n, d, cbq, qnorms, grp == 8 ? 3 : 4,
-                               nq, probes, istat, s);
+            launch_coarse_pick(cp.p4_gmax, gld, 32 * cp.tiles, nprobe, nprobe, ix->coarse_metric, qvars,
+                               (int64_t)maxv * qstride, cs->rows, cs->norms, cs->n, d, cbq, qnorms, 3, nq, probes,
+                               istat, s);
             MQVS_HIP(hipGetLastError());
             picked = true;
         }
@@ -1087,7 +1079,7 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
     if (prune) {
         craw = (float *)ws.craw.get(sizeof(float) * (size_t)nq * R);
         ibq = (float *)ws.ibq.get(sizeof(float) * (size_t)nq);
-        if (split && late_fork) qdelta = (float *)ws.qdelta.get(sizeof(float) * (size_t)nq);
+        if (split) qdelta = (float *)ws.qdelta.get(sizeof(float) * (size_t)nq);
         if (!qrec0) {
             qrec0 = (float *)ws.crec.get(sizeof(float) * kMxRec * (size_t)nq);
             launch_to_hi(qvars, nq, d, (int64_t)maxv * qstride, ix->dpad, 1, rup(nq, 16), nullptr, qrec0, nullptr, s);
@@ -1101,7 +1093,7 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
         launch_query_bound(bp, ix->metric, seg->ynorm_max, qrec0, ix->yrec, ibq, s);
         MQVS_HIP(hipGetLastError());
     }
-    if (split && late_fork) fork_chain();
+    if (split) fork_chain();
 
     // ---- fine: the probed lists
     int64_t *dstats = nullptr;
@@ -1158,18 +1150,7 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
             pr.ymax = seg->ynorm_max;
             pr.qdelta = qdelta;
         }
-        // over waves (k_rerank_plan + k_exact_records_w + k_sort_emit): the
-        // pruned candidates of every query spread over the chip (mode 3,
-        // nprobe 1: see DESIGN 3.7); MQVS_IVF_RR=0 (measurement build): one
-        // workgroup per query
-        bool wide = false;
-        if (R <= kSortCap && tune_int("MQVS_IVF_RR", 0) == 1) {
-            auto *sv = (uint32_t *)ws.rsurv.get(sizeof(uint32_t) * (size_t)nq * R);
-            auto *sc = (int *)ws.rcnt.get(sizeof(int) * (size_t)nq);
-            auto *sr = (uint4 *)ws.rrecs.get(sizeof(uint4) * (size_t)nq * R);
-            wide = launch_rerank_ids_wide(rp, ix->metric, crow, R, k, seg->row_offset, dids, ddist, pr, sv, sc, sr, s);
-        }
-        if (!wide) launch_rerank_ids(rp, ix->metric, crow, R, k, seg->row_offset, dids, ddist, rscr, s, pr);
+        launch_rerank_ids(rp, ix->metric, crow, R, k, seg->row_offset, dids, ddist, rscr, s, pr);
         MQVS_HIP(hipGetLastError());
         MQVS_HIP(hipEventRecord(ws.ev[5], s));
     }

@@ -27,7 +27,6 @@
 // stage consumed before, whose buffer is re-issued right after the barrier),
 // then the MFMA work.  No __syncthreads() in the loop: its fence would drain
 // the in-flight LDS-DMA (cdna_hip_programming.md, "Pipelining across barriers").
-#include <cstdio>
 #include <atomic>
 #include <cstdlib>
 
@@ -130,29 +129,6 @@ __device__ inline void wait_barrier() {
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
 }
 
-// raw s_barrier, no memory-op or MFMA movement across it
-__device__ inline void raw_barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-// s_waitcnt vmcnt(pend * P), pend in [0, DMAX - 1] (a runtime count: the tail
-// of a loop issues fewer stages)
-template <int P, int DMAX>
-__device__ inline void wait_vm(int pend) {
-    __builtin_amdgcn_sched_barrier(0);
-    if (DMAX >= 4 && pend >= 3)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(P * 3) : "memory");
-    else if (DMAX >= 3 && pend >= 2)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(P * 2) : "memory");
-    else if (DMAX >= 2 && pend >= 1)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(P * 1) : "memory");
-    else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-
 template <int GPW, int NBUF>
 __device__ inline void wait_stage(int pending) {
     // pending: stages issued after the one about to be consumed (0 .. NBUF-2)
@@ -170,22 +146,7 @@ __device__ inline void wait_stage(int pending) {
 // rows x 32 QB queries, 32x32x16 bf16 MFMA blocks; workgroup -> (row tile,
 // query block) with the query blocks of a row tile on one XCD (its L2 serves
 // the tile's re-reads).
-//
-// PP (ping-pong): the two waves of a SIMD (waves w and w + 4: the query halves
-// wq = 0 / 1) run one barrier apart, so that while one computes its 16 MFMAs of
-// a stage the other reads its fragments of the next stage from LDS and issues
-// its LDS-DMA pieces; the MFMA pipe then never waits for a wave's own reads /
-// DMA issue (the lock-step loop leaves it idle during both: 18 ms compute-only
-// against 6.6 ms of MFMA cycles at 10M x 768, nq 1000).  Every barrier is a
-// raw s_barrier; a stage is ready for reading after a barrier that every
-// issuing wave reached past a counted vmcnt covering its pieces; a buffer is
-// re-issued only after the barrier that follows the last MFMA phase reading
-// it.  Stages are issued D = NBUF - 2 ahead.
-// DIAG (diagnostic builds, wrong results): 1 = row pieces read from the first
-// 8 tiles only (an L2-resident row stream), 2 = query pieces from query
-// group 0 only, 4 = query pieces not issued, 8 = row pieces not issued (the
-// stage then holds stale bytes; the waits count only the issued pieces).
-template <int METRIC, bool PROBE, int WQ, int QB, int NBUF, int PP = 0, int DIAG = 0>
+template <int METRIC, bool PROBE, int WQ, int QB, int NBUF>
 __global__ __launch_bounds__(256 * WQ) void k_scan_hi(ScanParams p) {
     constexpr int WR = 4;
     constexpr int NW = WR * WQ;
@@ -242,26 +203,20 @@ __global__ __launch_bounds__(256 * WQ) void k_scan_hi(ScanParams p) {
             const int64_t gp = r0 + r;
             u = gp < r1 ? row_at(p, gp) : -1;
             if (u < 0) u = row_at(p, r0);  // padding: any real row, results discarded
-            if (DIAG & 1) u = (ti & 7) * RT + r;
             plane = p.rows_hi;
         } else {
             int j = q0 + r;
             if (j >= p.nq) j = 0;
-            if (DIAG & 2) j = r & 15;
             u = (int64_t)variant_of(p, j, ord) * p.q_vpad + j;
             plane = p.q_hi;
         }
         src[i] = reinterpret_cast<const unsigned char *>(plane) +
                  ((u >> 4) * nb * 1024 + plane_vec_off((uint32_t)(u & 15)) + c * 16);
     }
-    static_assert(GY % NW == 0, "row pieces: whole rounds of the waves");
-    constexpr int YPW = GY / NW;  // pieces i < YPW are row pieces, the rest query pieces
     auto issue = [&](int s) {
         unsigned char *dst = lds + (s % NBUF) * STAGE;
 #pragma unroll
         for (int i = 0; i < GPW; ++i) {
-            if ((DIAG & 8) && i < YPW) continue;
-            if ((DIAG & 4) && i >= YPW) continue;
             __builtin_amdgcn_global_load_lds((const void *)(src[i] + plane_step_off((uint32_t)s)),
                                              (lds_void *)(dst + (w + i * NW) * 1024), 16, 0, 0);
         }
@@ -282,88 +237,38 @@ __global__ __launch_bounds__(256 * WQ) void k_scan_hi(ScanParams p) {
         for (int jb = 0; jb < QB; ++jb) acc[i][jb] = f32x16{0};
 
     const int nst = (int)(p.dpad / HI_K);
-    constexpr int NPW = GPW - ((DIAG & 8) ? YPW : 0) - ((DIAG & 4) ? GPW - YPW : 0);  // pieces per wave, stage
-    if constexpr (PP) {
-        static_assert(WQ == 2 && NBUF >= 3, "ping-pong: two query halves, stages issued NBUF - 2 ahead");
-        constexpr int D = NBUF - 2;
-        const int grp = wq;  // waves w and w + 4 share a SIMD
-        auto stage_frags = [&](int s, bf16x8 (&ah)[2][2], bf16x8 (&bh)[2][QB]) {
-            const unsigned char *st = lds + (s % NBUF) * STAGE;
 #pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const int c = 2 * kk + h;
-#pragma unroll
-                for (int i = 0; i < 2; ++i) ah[kk][i] = frag(st, ra0 + 32 * i, c);
-#pragma unroll
-                for (int jb = 0; jb < QB; ++jb) bh[kk][jb] = frag(st + OFF_Q, rq0 + 32 * jb, c);
-            }
-        };
-        // prologue: stages 0 .. D-1 issued, stage 0 landed for everyone
-#pragma unroll
-        for (int s = 0; s < D; ++s)
-            if (s < nst) issue(s);
-        wait_vm<NPW, D>(nst - 1 < D - 1 ? nst - 1 : D - 1);
-        raw_barrier();
-        if (grp == 1) raw_barrier();
-        for (int s = 0; s < nst; ++s) {
-            bf16x8 ah[2][2], bh[2][QB];
-            // read phase (the partner wave computes meanwhile)
-            stage_frags(s, ah, bh);
-            if (s + D < nst) issue(s + D);
-            // pieces younger than stage s+1's, which the barrier after the
-            // partner's next read phase must find landed
-            const int pend = (nst - 2 - s) < D - 1 ? (nst - 2 - s) : D - 1;
-            if (grp == 1 && s + 1 < nst) wait_vm<NPW, D>(pend);
-            raw_barrier();
-            // MFMA phase (the partner reads meanwhile)
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int jb = 0; jb < QB; ++jb)
-                        acc[i][jb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[kk][i], bh[kk][jb], acc[i][jb], 0, 0,
-                                                                             0);
-            __builtin_amdgcn_s_setprio(0);
-            if (grp == 0 && s + 1 < nst) wait_vm<NPW, D>(pend);
-            raw_barrier();
+    for (int s = 0; s < NBUF - 1; ++s)
+        if (s < nst) issue(s);
+    for (int s = 0; s < nst; ++s) {
+        const int after = nst - 1 - s;  // stages after s
+        wait_stage<GPW, NBUF>(after < NBUF - 2 ? after : NBUF - 2);
+        // every wave is past its reads of stage s-1: its buffer takes stage s+NBUF-1
+        if (s + NBUF - 1 < nst) {
+            __builtin_amdgcn_sched_barrier(0);
+            issue(s + NBUF - 1);
+            __builtin_amdgcn_sched_barrier(0);
         }
-        if (grp == 0) raw_barrier();
-    } else {
+        const unsigned char *st = lds + (s % NBUF) * STAGE;
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-        for (int s = 0; s < NBUF - 1; ++s)
-            if (s < nst) issue(s);
-        for (int s = 0; s < nst; ++s) {
-            const int after = nst - 1 - s;  // stages after s
-            wait_stage<NPW, NBUF>(after < NBUF - 2 ? after : NBUF - 2);
-            // every wave is past its reads of stage s-1: its buffer takes stage s+NBUF-1
-            if (s + NBUF - 1 < nst) {
-                __builtin_amdgcn_sched_barrier(0);
-                issue(s + NBUF - 1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            const unsigned char *st = lds + (s % NBUF) * STAGE;
-            __builtin_amdgcn_s_setprio(1);
+        for (int kk = 0; kk < 2; ++kk) {
+            const int c = 2 * kk + h;
+            bf16x8 ah[2], bh[QB];
 #pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const int c = 2 * kk + h;
-                bf16x8 ah[2], bh[QB];
+            for (int i = 0; i < 2; ++i) ah[i] = frag(st, ra0 + 32 * i, c);
 #pragma unroll
-                for (int i = 0; i < 2; ++i) ah[i] = frag(st, ra0 + 32 * i, c);
+            for (int jb = 0; jb < QB; ++jb) bh[jb] = frag(st + OFF_Q, rq0 + 32 * jb, c);
 #pragma unroll
-                for (int jb = 0; jb < QB; ++jb) bh[jb] = frag(st + OFF_Q, rq0 + 32 * jb, c);
+            for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int jb = 0; jb < QB; ++jb)
-                        acc[i][jb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[jb], acc[i][jb], 0, 0, 0);
-            }
-            __builtin_amdgcn_s_setprio(0);
-            // (the next iteration's barrier orders these reads before the buffer
-            // is re-issued: the MFMAs consumed every fragment, so the reads retired)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                for (int jb = 0; jb < QB; ++jb)
+                    acc[i][jb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[jb], acc[i][jb], 0, 0, 0);
         }
+        __builtin_amdgcn_s_setprio(0);
+        // (the next iteration's barrier orders these reads before the buffer
+        // is re-issued: the MFMAs consumed every fragment, so the reads retired)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
@@ -389,7 +294,7 @@ __global__ __launch_bounds__(256 * WQ) void k_scan_hi(ScanParams p) {
 // NBLK: row blocks per wave -- 4 (256-row tiles), or 1 (kBfRowsSmall-row
 // tiles: short scans such as a few queries' probe, where 256-row tiles leave
 // most CUs idle and each wave's four blocks in a row set the time)
-template <int METRIC, bool PROBE, int NQB, int NST, bool NT = false, int NBLK = 4>
+template <int METRIC, bool PROBE, int NQB, int NST, int NBLK = 4>
 __global__ __launch_bounds__(256) void k_scan_hi_reg(ScanParams p) {
     constexpr int RT = 64 * NBLK;
     const int64_t ti = blockIdx.x / p.num_qblocks;
@@ -439,13 +344,9 @@ __global__ __launch_bounds__(256) void k_scan_hi_reg(ScanParams p) {
 #pragma unroll
         for (int s = 0; s < NST; ++s) {
             const bf16x4x2 *ps = reinterpret_cast<const bf16x4x2 *>(src + plane_step_off(s));
-            if constexpr (NT) {
-                // streaming rows (read once per search): non-temporal loads
-                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                a[buf][s] = __builtin_bit_cast(bf16x4x2, __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(ps)));
-            } else {
-                a[buf][s] = *ps;
-            }
+            // streaming rows (read once per search): non-temporal loads
+            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+            a[buf][s] = __builtin_bit_cast(bf16x4x2, __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(ps)));
         }
     };
     load(0, w);
@@ -482,18 +383,12 @@ static void launch_hi_reg(ScanParams p, hipStream_t s) {
     if (grid < 1) return;
     // rows streamed with non-temporal loads: 10M x 768 cosine main scan
     // 2.55 -> 2.28 ms at nq 1 (6.0 -> 6.7 TB/s), 2.80 -> 2.55 ms at nq 16,
-    // bit-identical (profiles/r02/smallnq/nt_ab.jsonl).  A/B switch
-    // (tools/ab_split.py): MQVS_HI_NT=0 = plain loads
-    const char *nte = tune_env("MQVS_HI_NT");
-    const bool nt = !(nte && nte[0] == '0');
+    // bit-identical (profiles/r02/smallnq/nt_ab.jsonl)
     switch (p.dpad / HI_K) {
 #define MQVS_HI_REG(N_)                                                                                        \
     case N_:                                                                                                   \
         if (p.tile_rows == kBfRowsSmall)                                                                       \
-            hipLaunchKernelGGL((k_scan_hi_reg<METRIC, PROBE, NQB, N_, true, 1>), dim3((unsigned)grid), dim3(256), \
-                               0, s, p);                                                                       \
-        else if (nt)                                                                                           \
-            hipLaunchKernelGGL((k_scan_hi_reg<METRIC, PROBE, NQB, N_, true>), dim3((unsigned)grid), dim3(256), 0, s, \
+            hipLaunchKernelGGL((k_scan_hi_reg<METRIC, PROBE, NQB, N_, 1>), dim3((unsigned)grid), dim3(256), 0, s, \
                                p);                                                                             \
         else                                                                                                   \
             hipLaunchKernelGGL((k_scan_hi_reg<METRIC, PROBE, NQB, N_>), dim3((unsigned)grid), dim3(256), 0, s, p); \
@@ -511,7 +406,7 @@ constexpr int kHiRegMaxDpad = 24 * HI_K;
 
 // A scan of nq queries that launch_scan_hi runs with k_scan_hi_reg<NQB = 1>,
 // which also takes kBfRowsSmall-row tiles (PROBE scans always reach it; main
-// scans when no tuned or batch kernel takes them first)
+// scans when no batch kernel takes them first)
 bool scan_hi_small_tiles_ok(int nq, int64_t dpad) {
     const char *reg = tune_env("MQVS_HI_REG");
     const bool use_reg = !(reg && reg[0] == '0');
@@ -519,36 +414,14 @@ bool scan_hi_small_tiles_ok(int nq, int64_t dpad) {
            dpad % (2 * HI_K) == 0 && dpad >= 2 * HI_K;
 }
 
-template <int METRIC, bool PROBE, int WQ, int QB, int NBUF, int PP = 0, int DIAG = 0>
+template <int METRIC, bool PROBE, int WQ, int QB, int NBUF>
 static void launch_hi_shape(ScanParams p, hipStream_t s) {
     constexpr int QT = 32 * QB * WQ;
     p.num_qblocks = (p.nq + QT - 1) / QT;
     const int64_t L = p.tiles * p.num_qblocks;
     if (L < 1) return;
     const int64_t grid = (L + 7) / 8 * 8;
-    hipLaunchKernelGGL((k_scan_hi<METRIC, PROBE, WQ, QB, NBUF, PP, DIAG>), dim3((unsigned)grid), dim3(256 * WQ), 0, s,
-                       p);
-}
-
-// Tuning override (tools/ab_split.py --tunes): MQVS_HI_TUNE="WQ,QB,NBUF[,PP[,DIAG]]"
-template <int METRIC, bool PROBE>
-static bool launch_hi_tuned(const ScanParams &p, hipStream_t s) {
-    const char *e = tune_env("MQVS_HI_TUNE");
-    int wq, qb, nbuf, pp = 0, diag = 0;
-    if (!e || !*e || std::sscanf(e, "%d,%d,%d,%d,%d", &wq, &qb, &nbuf, &pp, &diag) < 3) return false;
-    switch ((((wq * 10 + qb) * 10 + nbuf) * 100 + pp) * 100 + diag) {
-#define MQVS_HI_CASE(WQ_, QB_, NB_, PP_, DG_)                                         \
-    case (((WQ_ * 10 + QB_) * 10 + NB_) * 100 + PP_) * 100 + DG_:                     \
-        launch_hi_shape<METRIC, PROBE, WQ_, QB_, NB_, PP_, DG_>(p, s);                \
-        return true;
-        MQVS_HI_CASE(2, 4, 3, 0, 0) MQVS_HI_CASE(2, 4, 4, 0, 0)
-        MQVS_HI_CASE(2, 4, 4, 0, 2) MQVS_HI_CASE(2, 4, 4, 0, 12)
-        MQVS_HI_CASE(2, 4, 4, 1, 0) MQVS_HI_CASE(2, 4, 3, 1, 0) MQVS_HI_CASE(2, 4, 4, 1, 12)
-        MQVS_HI_CASE(2, 2, 3, 0, 0) MQVS_HI_CASE(2, 2, 4, 1, 0) MQVS_HI_CASE(2, 2, 3, 1, 0)
-        MQVS_HI_CASE(1, 2, 3, 0, 0)
-#undef MQVS_HI_CASE
-        default: return false;
-    }
+    hipLaunchKernelGGL((k_scan_hi<METRIC, PROBE, WQ, QB, NBUF>), dim3((unsigned)grid), dim3(256 * WQ), 0, s, p);
 }
 
 // set when a main-scan launch of this thread took the batch kernel
@@ -562,14 +435,11 @@ int take_batch_kernel_flag() {
 
 template <int METRIC, bool PROBE>
 static void launch_hi_t(const ScanParams &p, hipStream_t s) {
-    if constexpr (!PROBE)
-        if (launch_hi_tuned<METRIC, PROBE>(p, s)) return;
     if constexpr (!PROBE) {
         // batches: the one-wave-per-SIMD persistent scan (kernels_p4.hip) for
         // contiguous rows and identity chunk ordinals (measurement builds:
-        // MQVS_HI_PP=0 selects k_scan_hi instead).  (Round 2's 8-wave
-        // ping-pong kernel k_scan_hi_pp, 16.7 ms at nq 1000 against 13.5, is
-        // retired; profiles/r03/baseline_r02_kernels_ab.jsonl.)
+        // MQVS_HI_PP=0 forces k_scan_hi, the path such a scan takes when
+        // the batch kernel's launch conditions do not hold).
         const int pp = tune_int("MQVS_HI_PP", 2);
         if (p.nq > 128 && pp == 2 && launch_scan_p4(p, METRIC, s)) {
             g_batch_kernel_used = 1;

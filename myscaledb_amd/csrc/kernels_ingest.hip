@@ -24,7 +24,6 @@
 //   k_array_rows    the copy loop of :1381-1393: FLT_MAX fill, first
 //                   min(size, d) elements of a non-empty array, nonempty flag.
 #include "mqvs_internal.h"
-#include "tuning.h"
 
 namespace mqvs {
 
@@ -176,13 +175,8 @@ __device__ __forceinline__ uint32_t far_byte(const uint8_t *out, int32_t pos) {
 // wave per workgroup: its LDS accesses complete in program order, so a read
 // after a write sees it; the wave barriers only keep the compiler from moving
 // them.)  Positions are 32-bit (larger blocks are rejected as malformed).
-//
-// DIAG (measurement builds only; wrong output): 1 = parse only (no copies);
-// 2 = staging only, 4 = staging + pass A, 8 = staging + pass A + chain
-// (2, 4, 8: no status)
 constexpr int kChunk = 1024, kLook = 256, kSeg = kChunk / 64, kSpec = 4, kStarts = 4;
 constexpr int kMaxRec = kChunk / 3 + 2;  // tokens starting in a chunk (>= 3 bytes each but the last)
-template <int DIAG>
 __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *src, int64_t src_bytes, const IngestBlock *tab,
                                                       int64_t nblocks, uint8_t *dst, int *status) {
     __shared__ __attribute__((aligned(16))) uint8_t ring[kRing];
@@ -464,7 +458,6 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *src, int64_
                     if (u * 64 + lane < (int)(sizeof(cinw) / 4)) cinw[u * 64 + lane] = v[u];
             }
             __builtin_amdgcn_wave_barrier();
-            if (DIAG & 2) continue;
             const int32_t s0 = cs + kSeg * lane, s1 = s0 + kSeg;  // this lane's segment
             // ---- pass A: speculative parses of the segment from its first
             // kStarts bytes (one start per byte: on quantised floats, tokens
@@ -504,10 +497,6 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *src, int64_
                 xs[c] = x;
                 ts[c] = t;
                 ns[c] = nn;
-            }
-            if (DIAG & 4) {
-                if (__ballot(xs[0] == 12345 && ts[1] == 7 && ns[2] == 9 && xs[3] == 3) != 0) bad = true;
-                continue;
             }
             // ---- the true chain over the segments (uniform)
             // (segments without a true token start keep vE = isz: no pass B;
@@ -581,11 +570,6 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *src, int64_
                 bad = true;
                 break;
             }
-            if (DIAG & 8) {
-                if (__ballot(vE == 12345 && vO == 7 && vR == 9) != 0) bad = true;
-                E = cs + kChunk;
-                continue;
-            }
             // ---- pass B: records from the true entries
             bool lbad = false;
             {
@@ -614,10 +598,6 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *src, int64_
             // the next chunk holding a token start
             ncs = E - E % kChunk > cs ? E - E % kChunk : cs + kChunk;
             __builtin_amdgcn_wave_barrier();
-            if (DIAG & 1) {
-                op = O;
-                continue;
-            }
             // ---- run the records, up to 64 at a time
             for (int32_t r0 = 0; r0 < R;) {
                 r0 = __builtin_amdgcn_readfirstlane(r0);
@@ -745,7 +725,6 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *src, int64_
             }
         }
         bad = bad || !done || op != osz;
-        if (DIAG & 14) bad = false;
         __builtin_amdgcn_wave_barrier();
         if (!bad) flush(op);
         if (bad && lane == 0) atomicOr(status, 4);
@@ -1048,18 +1027,7 @@ void launch_decode_blocks(const uint8_t *src, int64_t src_bytes, const IngestBlo
                           int *status, hipStream_t s) {
     if (nblocks <= 0) return;
     const int grid = (int)std::min<int64_t>(nblocks, 4096);
-    // (diagnostics on the big stream only: the array sizes must decode)
-    const int diag = kDebugTuning && nblocks > 64 ? tune_int("MQVS_LZ4_DIAG", 0) : 0;
-    if (kDebugTuning && diag == 1)
-        hipLaunchKernelGGL(k_decode_blocks<1>, dim3(grid), dim3(64), 0, s, src, src_bytes, tab, nblocks, dst, status);
-    else if (kDebugTuning && diag == 2)
-        hipLaunchKernelGGL(k_decode_blocks<2>, dim3(grid), dim3(64), 0, s, src, src_bytes, tab, nblocks, dst, status);
-    else if (kDebugTuning && diag == 4)
-        hipLaunchKernelGGL(k_decode_blocks<4>, dim3(grid), dim3(64), 0, s, src, src_bytes, tab, nblocks, dst, status);
-    else if (kDebugTuning && diag == 8)
-        hipLaunchKernelGGL(k_decode_blocks<8>, dim3(grid), dim3(64), 0, s, src, src_bytes, tab, nblocks, dst, status);
-    else
-        hipLaunchKernelGGL(k_decode_blocks<0>, dim3(grid), dim3(64), 0, s, src, src_bytes, tab, nblocks, dst, status);
+    hipLaunchKernelGGL(k_decode_blocks, dim3(grid), dim3(64), 0, s, src, src_bytes, tab, nblocks, dst, status);
 }
 
 void launch_block_checksum(const uint8_t *src, const IngestBlock *tab, int64_t nblocks, int flag, int *status,

@@ -85,123 +85,13 @@ __global__ __launch_bounds__(256) void k_plan_count(IvfParams p) {
     }
 }
 
-// Workgroup b owns lists [b 16 kPlanThreads, (b + 1) 16 kPlanThreads): wave
-// w of it owns S of them (S a multiple of 64) and walks them 64 at a time,
-// lane l on list w S + 64 s + l, so every load is coalesced; the (pair count,
-// length) of its <= 16 steps stay in registers.  The three prefix sums (pairs,
-// work items, streamed rows) are wave scans with a carry, then one combine
-// over the 16 wave totals and, with more than one workgroup, the totals of the
-// workgroups before (bsum, written by the SUMS pass of the same kernel).
-// (One workgroup walking 39063 lists took 0.074 ms; three take ~0.01.)
-template <bool SUMS>
-__global__ __launch_bounds__(kPlanThreads) void k_plan_lists_reg(IvfParams p) {
-    constexpr int ST = 16;
-    constexpr int NWV = kPlanThreads / 64;
-    __shared__ int64_t sh[3][NWV];
-    const int base = blockIdx.x * ST * kPlanThreads;
-    const int L = min(p.nlist - base, ST * kPlanThreads);
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int S = ((L + NWV - 1) / NWV + 63) / 64 * 64;
-    const int qs = p.qg == 64 ? 6 : p.qg == 32 ? 5 : 4;  // qg is 16, 32 or 64
-    int cnt[ST], len[ST];
-#pragma unroll
-    for (int u = 0; u < ST; ++u) {
-        const int i = wv * S + 64 * u + lane;
-        const bool in = 64 * u < S && i < L;
-        cnt[u] = in ? p.lcount[base + i] : 0;
-        len[u] = in ? (int)(p.list_off[base + i + 1] - p.list_off[base + i]) : 0;
-    }
-    auto items_of = [&](int u) { return (int64_t)((cnt[u] + p.qg - 1) >> qs) * ((len[u] + p.chunk - 1) / p.chunk); };
-    auto rows_of = [&](int u) { return (int64_t)((cnt[u] + p.qg - 1) >> qs) * len[u]; };
-    int64_t w0 = 0, w1 = 0, w2 = 0;
-#pragma unroll
-    for (int u = 0; u < ST; ++u) {
-        w0 += cnt[u];
-        w1 += items_of(u);
-        w2 += rows_of(u);
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        w0 += __shfl_xor(w0, o);
-        w1 += __shfl_xor(w1, o);
-        w2 += __shfl_xor(w2, o);
-    }
-    if (lane == 0) {
-        sh[0][wv] = w0;
-        sh[1][wv] = w1;
-        sh[2][wv] = w2;
-    }
-    __syncthreads();
-    if (SUMS) {
-        if (t < 3) {
-            int64_t v = 0;
-            for (int w = 0; w < NWV; ++w) v += sh[t][w];
-            p.bsum[3 * blockIdx.x + t] = v;
-        }
-        return;
-    }
-    int64_t c0 = 0, c1 = 0, t1 = 0, t2 = 0;
-    for (int w = 0; w < NWV; ++w) {
-        if (w < wv) {
-            c0 += sh[0][w];
-            c1 += sh[1][w];
-        }
-        t1 += sh[1][w];
-        t2 += sh[2][w];
-    }
-    if (gridDim.x > 1) {
-        t1 = t2 = 0;
-        for (int b = 0; b < (int)gridDim.x; ++b) {
-            if (b < (int)blockIdx.x) {
-                c0 += p.bsum[3 * b];
-                c1 += p.bsum[3 * b + 1];
-            }
-            t1 += p.bsum[3 * b + 1];
-            t2 += p.bsum[3 * b + 2];
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < ST; ++u) {
-        if (64 * u >= S) break;  // wave-uniform
-        const int64_t v0 = cnt[u], v1 = items_of(u);
-        int64_t i0 = v0, i1 = v1;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int64_t y0 = __shfl_up(i0, o), y1 = __shfl_up(i1, o);
-            if (lane >= o) {
-                i0 += y0;
-                i1 += y1;
-            }
-        }
-        const int i = wv * S + 64 * u + lane;
-        if (i < L) {
-            p.lstart[base + i] = c0 + i0 - v0;
-            p.lfill[base + i] = 0;  // the scatter's cursors (no memset of their own)
-            int64_t r1 = c1 + i1 - v1;
-            const int g = (cnt[u] + p.qg - 1) >> qs;
-            const int nc = (len[u] + p.chunk - 1) / p.chunk;
-            for (int j = 0; j < g; ++j)
-                for (int cc = 0; cc < nc; ++cc) {
-                    p.item_list[r1] = base + i;
-                    p.item_grp[r1] = j;
-                    p.item_chk[r1] = cc;
-                    ++r1;
-                }
-        }
-        c0 += __shfl(i0, 63);
-        c1 += __shfl(i1, 63);
-    }
-    if (t == 0 && blockIdx.x == 0) {
-        *p.nitems = (int)t1;
-        p.stats[1] = t1;
-        p.stats[2] = t2 * p.dpad * 2;
-        p.stats[3] = (int64_t)p.nq * p.nprobe;
-    }
-}
-
 // Workgroup b owns kPlanBlk lists: their (pair count, length) are staged in
 // LDS by coalesced loads, then thread t walks lists [kPlanPer t, kPlanPer (t +
-// 1)) sequentially, so the block does one wave scan per prefix sum instead of
-// one per 64 lists (the register walk above: 35 us for 39063 lists in 3
-// workgroups).  Multi-workgroup carries as above (bsum, SUMS pass).
+// 1)) sequentially, so the block does one wave scan per prefix sum.  The
+// three prefix sums (pairs, work items, streamed rows) are wave scans, then
+// one combine over the wave totals and, with more than one workgroup, the
+// totals of the workgroups before (bsum, written by the SUMS pass of the same
+// kernel).
 constexpr int kPlanPer = 4;
 constexpr int kPlanBlk = kPlanPer * kPlanThreads;
 
@@ -292,96 +182,6 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_lists_blk(IvfParams p) {
         c0 += c;
     }
     if (t == 0 && blockIdx.x == 0) {
-        *p.nitems = (int)t1;
-        p.stats[1] = t1;
-        p.stats[2] = t2 * p.dpad * 2;
-        p.stats[3] = (int64_t)p.nq * p.nprobe;
-    }
-}
-
-// One workgroup for any nlist: the same wave-strided layout with the per-list
-// values loaded again in the second pass instead of kept in registers.  Kept
-// for A/B (MQVS_IVF_PLAN=1, measurement build); the default is
-// k_plan_lists_blk above.  (A contiguous run of lists per
-// thread made every load of a wave touch 64 different lines: 0.27 ms of plan
-// at 39063 lists against 0.05 at 10000.)
-__global__ __launch_bounds__(kPlanThreads) void k_plan_lists(IvfParams p) {
-    constexpr int NWV = kPlanThreads / 64;
-    __shared__ int64_t sh[3][NWV];
-    const int L = p.nlist;
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int S = ((L + NWV - 1) / NWV + 63) / 64 * 64;
-    const int qs = p.qg == 64 ? 6 : p.qg == 32 ? 5 : 4;  // qg is 16, 32 or 64
-    auto load = [&](int u, int &cnt, int &len) {
-        const int i = wv * S + 64 * u + lane;
-        const bool in = i < L;
-        cnt = in ? p.lcount[i] : 0;
-        len = in ? (int)(p.list_off[i + 1] - p.list_off[i]) : 0;
-    };
-    auto items_of = [&](int cnt, int len) {
-        return (int64_t)((cnt + p.qg - 1) >> qs) * ((len + p.chunk - 1) / p.chunk);
-    };
-    int64_t w0 = 0, w1 = 0, w2 = 0;
-    const int steps = S / 64;
-#pragma unroll 8
-    for (int u = 0; u < steps; ++u) {
-        int cnt, len;
-        load(u, cnt, len);
-        w0 += cnt;
-        w1 += items_of(cnt, len);
-        w2 += (int64_t)((cnt + p.qg - 1) >> qs) * len;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        w0 += __shfl_xor(w0, o);
-        w1 += __shfl_xor(w1, o);
-        w2 += __shfl_xor(w2, o);
-    }
-    if (lane == 0) {
-        sh[0][wv] = w0;
-        sh[1][wv] = w1;
-        sh[2][wv] = w2;
-    }
-    __syncthreads();
-    int64_t c0 = 0, c1 = 0, t1 = 0, t2 = 0;
-    for (int w = 0; w < NWV; ++w) {
-        if (w < wv) {
-            c0 += sh[0][w];
-            c1 += sh[1][w];
-        }
-        t1 += sh[1][w];
-        t2 += sh[2][w];
-    }
-    for (int u = 0; u < steps; ++u) {
-        int cnt, len;
-        load(u, cnt, len);
-        const int64_t v0 = cnt, v1 = items_of(cnt, len);
-        int64_t i0 = v0, i1 = v1;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int64_t y0 = __shfl_up(i0, o), y1 = __shfl_up(i1, o);
-            if (lane >= o) {
-                i0 += y0;
-                i1 += y1;
-            }
-        }
-        const int i = wv * S + 64 * u + lane;
-        if (i < L) {
-            p.lstart[i] = c0 + i0 - v0;
-            p.lfill[i] = 0;
-            int64_t r1 = c1 + i1 - v1;
-            const int g = (cnt + p.qg - 1) >> qs;
-            const int nc = (len + p.chunk - 1) / p.chunk;
-            for (int j = 0; j < g; ++j)
-                for (int cc = 0; cc < nc; ++cc) {
-                    p.item_list[r1] = i;
-                    p.item_grp[r1] = j;
-                    p.item_chk[r1] = cc;
-                    ++r1;
-                }
-        }
-        c0 += __shfl(i0, 63);
-        c1 += __shfl(i1, 63);
-    }
-    if (t == 0) {
         *p.nitems = (int)t1;
         p.stats[1] = t1;
         p.stats[2] = t2 * p.dpad * 2;
@@ -609,16 +409,14 @@ __device__ inline void ivf_pair_stats(const IvfRegions &g, int q, int64_t T, boo
 // one load instruction covers a contiguous 64-B half-window of 16 rows.
 // kIvfWin windows are in flight per lane and the next group is prefetched
 // while the current one feeds the MFMAs; every A fragment serves QB MFMAs.
-template <int METRIC, int QB, bool NTL>
+template <int METRIC, int QB>
 __global__ __launch_bounds__(256) void k_ivf_scan(IvfParams p) {
     constexpr int QG = 16 * QB;
     // plane reads: each probed list's rows are read once per query group
-    // (NTL: non-temporal, kept out of the caches' retention)
+    // (non-temporal: kept out of the caches' retention)
     auto ldp = [](const uint16_t *a) __attribute__((always_inline)) {
         typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-        if (NTL)
-            return __builtin_bit_cast(ivf_bf16x8, __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(a)));
-        return *reinterpret_cast<const ivf_bf16x8 *>(a);
+        return __builtin_bit_cast(ivf_bf16x8, __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(a)));
     };
     extern __shared__ __attribute__((aligned(16))) unsigned char qtile[];  // QG x (2 dpad + 16) B
     __shared__ int s_ent[QG];
@@ -1097,7 +895,7 @@ void launch_iota_probes(int64_t *probes, int nq, int np, hipStream_t s) {
 
 void launch_ivf_plan(const IvfParams &p, hipStream_t s) {
     const int64_t E = (int64_t)p.nq * p.nprobe;
-    if (E <= kPlanSmallE && tune_int("MQVS_IVF_PLAN", 0) == 0) {
+    if (E <= kPlanSmallE) {
         hipLaunchKernelGGL(k_plan_small, dim3(1), dim3(kPlanThreads), 0, s, p);
         return;
     }
@@ -1106,25 +904,14 @@ void launch_ivf_plan(const IvfParams &p, hipStream_t s) {
     launch_fill2(reinterpret_cast<uint32_t *>(p.lcount), p.nlist, 0u, nullptr, 0, 0u, s);
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((std::max(E, (int64_t)p.nq) + 255) / 256, 2048));
     hipLaunchKernelGGL(k_plan_count, dim3(grid), dim3(256), 0, s, p);
-    // A/B (measurement build): 1 one workgroup, 2 register walk, 3 the list
-    // kernels even for few pairs (k_plan_small above otherwise)
-    const int plan = tune_int("MQVS_IVF_PLAN", 0);
-    if (plan == 1) {
-        hipLaunchKernelGGL(k_plan_lists, dim3(1), dim3(kPlanThreads), 0, s, p);
-    } else if (plan == 2) {
-        const int nb = (p.nlist + 16 * kPlanThreads - 1) / (16 * kPlanThreads);
-        if (nb > 1) hipLaunchKernelGGL(k_plan_lists_reg<true>, dim3(nb), dim3(kPlanThreads), 0, s, p);
-        hipLaunchKernelGGL(k_plan_lists_reg<false>, dim3(std::max(nb, 1)), dim3(kPlanThreads), 0, s, p);
-    } else {
-        const int nb = (p.nlist + kPlanBlk - 1) / kPlanBlk;
-        if (nb > 1) hipLaunchKernelGGL(k_plan_lists_blk<true>, dim3(nb), dim3(kPlanThreads), 0, s, p);
-        hipLaunchKernelGGL(k_plan_lists_blk<false>, dim3(std::max(nb, 1)), dim3(kPlanThreads), 0, s, p);
-    }
+    const int nb = (p.nlist + kPlanBlk - 1) / kPlanBlk;
+    if (nb > 1) hipLaunchKernelGGL(k_plan_lists_blk<true>, dim3(nb), dim3(kPlanThreads), 0, s, p);
+    hipLaunchKernelGGL(k_plan_lists_blk<false>, dim3(std::max(nb, 1)), dim3(kPlanThreads), 0, s, p);
     hipLaunchKernelGGL(k_plan_scatter, dim3(grid), dim3(256), 0, s, p);
     hipLaunchKernelGGL(k_plan_queries, dim3(1), dim3(kPlanThreads), 0, s, p);
 }
 
-template <int QB, bool NTL>
+template <int QB>
 static void ivf_scan_t(const IvfParams &p, int metric, int grid, hipStream_t s) {
     const size_t lds = (size_t)16 * QB * (2 * p.dpad + 16);
     // (the caller sizes p.qg with ivf_fit_qg; a tile that does not fit is
@@ -1133,41 +920,33 @@ static void ivf_scan_t(const IvfParams &p, int metric, int grid, hipStream_t s) 
         fail(MQVS_ERR_LOGICAL, "ivf scan: " + std::to_string(16 * QB) + "-query tile of " + std::to_string(p.dpad) +
                                    " padded dimensions exceeds the workgroup's LDS");
     if (lds > 65536) {  // 64-query tiles of wide rows: opt in to more than 64 KiB of LDS
-        MQVS_HIP(hipFuncSetAttribute((const void *)k_ivf_scan<MQVS_METRIC_L2, QB, NTL>,
+        MQVS_HIP(hipFuncSetAttribute((const void *)k_ivf_scan<MQVS_METRIC_L2, QB>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MQVS_HIP(hipFuncSetAttribute((const void *)k_ivf_scan<MQVS_METRIC_IP, QB, NTL>,
+        MQVS_HIP(hipFuncSetAttribute((const void *)k_ivf_scan<MQVS_METRIC_IP, QB>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MQVS_HIP(hipFuncSetAttribute((const void *)k_ivf_scan<MQVS_METRIC_COSINE, QB, NTL>,
+        MQVS_HIP(hipFuncSetAttribute((const void *)k_ivf_scan<MQVS_METRIC_COSINE, QB>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     switch (metric) {
         case MQVS_METRIC_L2:
-            hipLaunchKernelGGL((k_ivf_scan<MQVS_METRIC_L2, QB, NTL>), dim3(grid), dim3(256), lds, s, p);
+            hipLaunchKernelGGL((k_ivf_scan<MQVS_METRIC_L2, QB>), dim3(grid), dim3(256), lds, s, p);
             break;
         case MQVS_METRIC_IP:
-            hipLaunchKernelGGL((k_ivf_scan<MQVS_METRIC_IP, QB, NTL>), dim3(grid), dim3(256), lds, s, p);
+            hipLaunchKernelGGL((k_ivf_scan<MQVS_METRIC_IP, QB>), dim3(grid), dim3(256), lds, s, p);
             break;
         default:
-            hipLaunchKernelGGL((k_ivf_scan<MQVS_METRIC_COSINE, QB, NTL>), dim3(grid), dim3(256), lds, s, p);
+            hipLaunchKernelGGL((k_ivf_scan<MQVS_METRIC_COSINE, QB>), dim3(grid), dim3(256), lds, s, p);
             break;
     }
 }
 
-template <bool NTL>
-static void ivf_scan_nt(const IvfParams &p, int metric, int grid, hipStream_t s) {
-    if (p.qg == 64)
-        ivf_scan_t<4, NTL>(p, metric, grid, s);
-    else if (p.qg == 32)
-        ivf_scan_t<2, NTL>(p, metric, grid, s);
-    else
-        ivf_scan_t<1, NTL>(p, metric, grid, s);
-}
-
 void launch_ivf_scan(const IvfParams &p, int metric, int grid, hipStream_t s) {
-    if (tune_int("MQVS_IVF_NT", 1) == 1)
-        ivf_scan_nt<true>(p, metric, grid, s);
+    if (p.qg == 64)
+        ivf_scan_t<4>(p, metric, grid, s);
+    else if (p.qg == 32)
+        ivf_scan_t<2>(p, metric, grid, s);
     else
-        ivf_scan_nt<false>(p, metric, grid, s);
+        ivf_scan_t<1>(p, metric, grid, s);
 }
 
 void launch_ivf_select(const Cand *cand, const IvfRegions &rg, int nq, int R, int metric, int64_t *out_rows,

@@ -334,12 +334,10 @@ __device__ inline float wave_exact(const ScanParams &p, int q, int64_t row, floa
 // discarded; the ring's refills past the last tile re-read it), so the
 // compiler counts each wait exactly: wave_exact waits a full random-row load
 // latency per tile (one tile ahead), ~24 latencies per wave at d = 768.
+// The query slice stays one tile ahead (registers are the index re-rank's
+// occupancy; three tiles ahead measured slower, DESIGN.md "retired variants").
 constexpr int kRrPF = 3;
-// XPF: tiles of the query slice in flight.  1 (the index re-rank: registers
-// are its occupancy) waits an L2 round trip for the query slice every tile --
-// the whole chain at small nq, where one workgroup's 24 tiles are the exact
-// stage (k_exact_records at nq 1: ~23 us); 3 keeps it in a ring like the rows.
-template <int METRIC, bool DIRECT, int NT, int XPF = 1>
+template <int METRIC, bool DIRECT, int NT>
 __device__ inline float wave_exact_nt(const ScanParams &p, int q, int64_t row, float *tile) {
     constexpr int d = 32 * NT;
     const int lane = threadIdx.x & 63;
@@ -359,7 +357,7 @@ __device__ inline float wave_exact_nt(const ScanParams &p, int q, int64_t row, f
             const int64_t r = __shfl(row, j * 8 + (lane >> 3));
             base[j] = p.rows + (r >= 0 ? r : 0) * d + (lane & 7) * 4;
         }
-        float4 ry[kRrPF][8], rx[XPF][8];
+        float4 ry[kRrPF][8], rx[8];
         auto load_y = [&](int t, float4(&dst)[8]) __attribute__((always_inline)) {
             const int tt = t < NT ? t : NT - 1;
 #pragma unroll
@@ -372,12 +370,10 @@ __device__ inline float wave_exact_nt(const ScanParams &p, int q, int64_t row, f
         };
 #pragma unroll
         for (int sl = 0; sl < kRrPF; ++sl) load_y(sl, ry[sl]);
-#pragma unroll
-        for (int sl = 0; sl < XPF; ++sl) load_x(sl, rx[sl]);
+        load_x(0, rx);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             float4(&cur)[8] = ry[t % kRrPF];
-            float4(&curx)[8] = rx[t % XPF];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 float *dst = tile + (j * 8 + (lane >> 3)) * kRrStride + (lane & 7) * 4;
@@ -389,13 +385,13 @@ __device__ inline float wave_exact_nt(const ScanParams &p, int q, int64_t row, f
             float xt[32];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                xt[4 * j] = curx[j].x;
-                xt[4 * j + 1] = curx[j].y;
-                xt[4 * j + 2] = curx[j].z;
-                xt[4 * j + 3] = curx[j].w;
+                xt[4 * j] = rx[j].x;
+                xt[4 * j + 1] = rx[j].y;
+                xt[4 * j + 2] = rx[j].z;
+                xt[4 * j + 3] = rx[j].w;
             }
             load_y(t + kRrPF, cur);
-            load_x(t + XPF, curx);
+            load_x(t + 1, rx);
             __builtin_amdgcn_wave_barrier();
             const float *mine = tile + lane * kRrStride;
 #pragma unroll
@@ -424,13 +420,13 @@ __device__ inline float wave_exact_nt(const ScanParams &p, int q, int64_t row, f
 }
 
 // wave_exact_nt for d = 768, wave_exact otherwise
-template <int METRIC, bool DIRECT, int XPF = 1>
+template <int METRIC, bool DIRECT>
 __device__ inline float wave_exact_any(const ScanParams &p, int q, int64_t row, float *tile) {
-    if (p.d == 768) return wave_exact_nt<METRIC, DIRECT, 24, XPF>(p, q, row, tile);
+    if (p.d == 768) return wave_exact_nt<METRIC, DIRECT, 24>(p, q, row, tile);
     return wave_exact<METRIC, DIRECT>(p, q, row, tile);
 }
 
-template <int METRIC, bool DIRECT, int XPF = 1>
+template <int METRIC, bool DIRECT>
 __global__ __launch_bounds__(SEL_THREADS) void k_rerank_ids_tiled(ScanParams p, const int64_t *cand, int ncand,
                                                                  int k, int64_t id_offset, int64_t *out_ids,
                                                                  float *out_dist, int nrec, uint4 *scratch,
@@ -453,110 +449,10 @@ __global__ __launch_bounds__(SEL_THREADS) void k_rerank_ids_tiled(ScanParams p, 
             row = c[i];
             if (!(row >= 0 && row < p.n && row_valid(p, row))) row = -1;
         }
-        const float raw = wave_exact_any<METRIC, DIRECT, XPF>(p, q, row, tile);
+        const float raw = wave_exact_any<METRIC, DIRECT>(p, q, row, tile);
         if (i < ncand) dst[i] = rerank_rec<METRIC>(p, row, raw);
     }
     rerank_emit<METRIC>(recs, g, ncand, k, q, id_offset, out_ids, out_dist);
-}
-
-// Two queries per workgroup (waves 0-1: query 2 b, waves 2-3: query 2 b + 1),
-// for up to kRrPairMax candidates: k_rerank_ids_tiled's chain and records,
-// each query's candidates 128 at a time over its two waves.  At ~233 VGPRs
-// two waves per SIMD fit -- two workgroups per CU: one query per workgroup
-// took two rounds of 1000 workgroups at nq 1000, each as long as a 24-tile
-// random-row chain, and after pruning (~120 of 200 candidates kept) half of
-// its waves had no rows; here 500 workgroups are one round.  The top k is
-// placed by rank counting over the kept prefix (records are unique: key, then
-// row; equal records -- a row listed twice -- rank by position, as a stable
-// sort), the same output as rerank_emit's sort.  Measured slower (mode 3,
-// nprobe 1, k 100: re-rank 127 -> 140 us; the rows arrive at ~2.9 TB/s either
-// way -- a torch index_select of the same rows runs at 2.5-2.8 TB/s,
-// tools/gather_tlb_probe.py -- so the random-row read rate bounds it, not the
-// rounds): MQVS_RR_PAIR=1, measurement build only.
-constexpr int kRrPairMax = 512;
-
-template <int METRIC, bool DIRECT>
-__global__ __launch_bounds__(SEL_THREADS) void k_rerank_ids_pair(ScanParams p, const int64_t *cand, int ncand,
-                                                                int k, int64_t id_offset, int64_t *out_ids,
-                                                                float *out_dist, RerankPrune pr) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ int s_m[2], s_ok[2], s_nv[2];
-    __shared__ float s_cut[2];
-    const int h = threadIdx.x >> 7, ht = threadIdx.x & 127, wv = threadIdx.x >> 6;
-    const int q = blockIdx.x * 2 + h;
-    const bool act = q < p.nq;
-    const int qq = act ? q : 0;
-    uint4 *recs = reinterpret_cast<uint4 *>(smem) + (size_t)h * ncand;
-    float *tile = reinterpret_cast<float *>(smem + 2 * (size_t)ncand * sizeof(uint4)) + wv * 64 * kRrStride;
-    if (ht == 0) {
-        s_m[h] = act ? ncand : 0;
-        s_ok[h] = 0;
-        s_nv[h] = 0;
-    }
-    // the cut (rerank_keep, per half): its first wave
-    if (act && pr.raw && k < ncand && ht < 64) {
-        float w = 0.f;
-        const bool ok = wave_prune_cut<METRIC>(p, pr, q, ncand, k, w);
-        if (ht == 0) {
-            s_cut[h] = w;
-            s_ok[h] = ok ? 1 : 0;
-        }
-    }
-    __syncthreads();
-    if (act && s_ok[h]) {
-        const float w = s_cut[h];
-        const float *raw = pr.raw + (int64_t)q * ncand;
-        for (int i = ht; i < ncand; i += 128) {
-            const float a = raw[i];
-            const bool keep = METRIC == MQVS_METRIC_L2 ? a <= w : a >= w;
-            if (!keep) {
-                atomicMin(&s_m[h], i);
-                break;
-            }
-        }
-    }
-    __syncthreads();
-    const int m = s_m[h];
-    if (act && ht == 0 && pr.count) atomicAdd(pr.count, (unsigned long long)m);
-    const int64_t *c = cand + (int64_t)qq * ncand;
-    for (int cb = 0; cb < ncand; cb += 128) {
-        const int i = cb + ht;
-        int64_t row = -1;
-        if (i < m) {
-            row = c[i];
-            if (!(row >= 0 && row < p.n && row_valid(p, row))) row = -1;
-        }
-        const float raw = cb < m ? wave_exact_any<METRIC, DIRECT>(p, qq, row, tile) : 0.f;
-        if (i < ncand) recs[i] = rerank_rec<METRIC>(p, row, raw);
-    }
-    __syncthreads();
-    // records at m and later are invalid (all ones: never less than a valid one)
-    if (act) {
-        for (int i = ht; i < m; i += 128) {
-            const uint4 e = recs[i];
-            if (e.x == 0xFFFFFFFFu) continue;
-            int rank = 0;
-            for (int o = 0; o < m; ++o) {
-                const uint4 f = recs[o];
-                rank += (rec_less(f, e) || (o < i && f.x == e.x && f.y == e.y && f.z == e.z && f.w == e.w)) ? 1 : 0;
-            }
-            atomicAdd(&s_nv[h], 1);
-            if (rank < k) {
-                out_ids[(int64_t)q * k + rank] = (int64_t)e.w + id_offset;
-                out_dist[(int64_t)q * k + rank] = key_to_value(METRIC, e.x);
-            }
-        }
-    }
-    __syncthreads();
-    if (act) {
-        const float pad = (METRIC == MQVS_METRIC_IP) ? 1.17549435e-38f
-                          : (METRIC == kMetricIpRaw) ? -3.40282347e+38f
-                                                     : 3.40282347e+38f;
-        for (int i = s_nv[h] + ht; i < k; i += 128) {
-            out_ids[(int64_t)q * k + i] = -1;
-            out_dist[(int64_t)q * k + i] = pad;
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -564,7 +460,7 @@ __global__ __launch_bounds__(SEL_THREADS) void k_rerank_ids_pair(ScanParams p, c
 // (mqvs_search path 2): query q's cnt[q] survivor rows are surv[q * rs + i];
 // their records go to recs[q * rs + i].  Work items (chunk of 256
 // survivors, query), chunk-major, walked grid-stride.
-template <int METRIC, bool DIRECT, bool XPF3 = true>
+template <int METRIC, bool DIRECT>
 __global__ __launch_bounds__(SEL_THREADS) void k_exact_records(ScanParams p, const uint32_t *surv, const int *cnt,
                                                               int64_t rs, int chunks, uint4 *recs) {
     __shared__ float tiles[(SEL_THREADS / 64) * 64 * kRrStride];
@@ -578,7 +474,7 @@ __global__ __launch_bounds__(SEL_THREADS) void k_exact_records(ScanParams p, con
         const int64_t row = i < m ? (int64_t)surv[(int64_t)q * rs + i] : -1;
         float raw;
         if ((p.d & 3) == 0)
-            raw = XPF3 ? wave_exact_any<METRIC, DIRECT, 3>(p, q, row, tile) : wave_exact_any<METRIC, DIRECT>(p, q, row, tile);
+            raw = wave_exact_any<METRIC, DIRECT>(p, q, row, tile);
         else
             raw = row >= 0 ? cand_value<METRIC, DIRECT>(p, q, row) : 0.f;
         if (i < m) recs[(int64_t)q * rs + i] = rerank_rec<METRIC>(p, row, raw);
@@ -698,10 +594,6 @@ void launch_exact_rerank(const ScanParams &p, int metric, const uint32_t *surv, 
     const bool one_wave = (p.d & 3) == 0 && p.nq <= tune_int("MQVS_RR_1W_NQ", 16);
     const int chunks64 = (cap + 63) / 64;
     const int grid64 = std::max(1, std::min(p.nq * chunks64, 16384));
-    // (measurement build A/B: MQVS_RR_XPF=1, the query slice one tile ahead)
-    // (query slice three tiles ahead measured slower: nq 1 23.2 -> 25.2 us,
-    // the index re-rank 124 -> 167 us)
-    const bool xpf1 = tune_int("MQVS_RR_XPF", 1) == 1;
 #define MQVS_ER(M)                                                                                                \
     do {                                                                                                          \
         if (one_wave && direct)                                                                                   \
@@ -710,12 +602,6 @@ void launch_exact_rerank(const ScanParams &p, int metric, const uint32_t *surv, 
         else if (one_wave)                                                                                        \
             hipLaunchKernelGGL((k_exact_records_1w<M, false>), dim3(grid64), dim3(64), 0, s, p, surv, cnt, rs,     \
                                chunks64, recs);                                                                   \
-        else if (xpf1 && direct)                                                                                  \
-            hipLaunchKernelGGL((k_exact_records<M, true, false>), dim3(grid), dim3(SEL_THREADS), 0, s, p, surv, cnt, \
-                               rs, chunks, recs);                                                                 \
-        else if (xpf1)                                                                                            \
-            hipLaunchKernelGGL((k_exact_records<M, false, false>), dim3(grid), dim3(SEL_THREADS), 0, s, p, surv,  \
-                               cnt, rs, chunks, recs);                                                            \
         else if (direct)                                                                                          \
             hipLaunchKernelGGL((k_exact_records<M, true>), dim3(grid), dim3(SEL_THREADS), 0, s, p, surv, cnt, rs, \
                                chunks, recs);                                                                     \
@@ -734,127 +620,16 @@ void launch_exact_rerank(const ScanParams &p, int metric, const uint32_t *surv, 
 #undef MQVS_ER
 }
 
-// ---------------------------------------------------------------------------
-// The index re-rank spread over waves instead of one workgroup per query
-// (R <= kSortCap, d % 4 == 0).  k_rerank_ids_tiled keeps every query's
-// candidates in one 4-wave workgroup: at ~233 VGPRs two waves per SIMD fit,
-// so 1000 queries took two rounds of workgroups and a workgroup lasts as long
-// as its slowest wave's 24-tile chain whether the bound pruned half its
-// candidates or not.  Here:
-//   k_rerank_plan      one wave per query: the pruned prefix (wave_prune_cut)
-//                      and its valid rows, compacted in candidate order;
-//   k_exact_records_w  work items of (64 candidates, query), chunk-major over
-//                      the queries, one per wave (the waves of a workgroup
-//                      take 4 consecutive queries' same chunk);
-//   k_sort_emit        the top k of each query's records, as mqvs_search.
-// Records and order are the ones k_rerank_ids_tiled produces.
-template <int METRIC>
-__global__ __launch_bounds__(256) void k_rerank_plan(ScanParams p, const int64_t *cand, int ncand, int k,
-                                                     RerankPrune pr, uint32_t *surv, int *cnt) {
-    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (q >= p.nq) return;
-    float w = 0.f;
-    const bool ok = pr.raw && k < ncand && wave_prune_cut<METRIC>(p, pr, q, ncand, k, w);
-    const int64_t *c = cand + (int64_t)q * ncand;
-    const float *raw = pr.raw ? pr.raw + (int64_t)q * ncand : nullptr;
-    uint32_t *out = surv + (int64_t)q * ncand;
-    int n = 0, m = ncand;
-    for (int i0 = 0; i0 < ncand; i0 += 64) {
-        const int i = i0 + lane;
-        bool keep = i < ncand;
-        if (ok && keep) {
-            const float a = raw[i];
-            keep = METRIC == MQVS_METRIC_L2 ? a <= w : a >= w;
-        }
-        const uint64_t km = __ballot(keep);
-        // the sorted candidates: the first one past the cut ends the prefix
-        const int stop = km == ~0ull ? 64 : __builtin_ctzll(~km);
-        const int64_t row = (i < ncand && lane < stop) ? c[i] : -1;
-        const bool v = row >= 0 && row < p.n && row_valid(p, row);
-        const uint64_t vm = __ballot(v);
-        if (v) out[n + __popcll(vm & ((1ull << lane) - 1ull))] = (uint32_t)row;
-        n += __popcll(vm);
-        if (stop < 64) {
-            m = i0 + stop;
-            break;
-        }
-    }
-    if (lane == 0) {
-        cnt[q] = n;
-        if (pr.count) atomicAdd(pr.count, (unsigned long long)m);
-    }
-}
-
-template <int METRIC, bool DIRECT>
-__global__ __launch_bounds__(SEL_THREADS) void k_exact_records_w(ScanParams p, const uint32_t *surv, const int *cnt,
-                                                                int64_t rs, int chunks, uint4 *recs) {
-    __shared__ float tiles[(SEL_THREADS / 64) * 64 * kRrStride];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float *tile = tiles + wv * 64 * kRrStride;
-    const int64_t items = (int64_t)p.nq * chunks;
-    const int64_t nw = (int64_t)gridDim.x * (SEL_THREADS / 64);
-    for (int64_t it = (int64_t)blockIdx.x * (SEL_THREADS / 64) + wv; it < items; it += nw) {
-        const int c = (int)(it / p.nq), q = (int)(it - (int64_t)c * p.nq);
-        const int m = cnt[q];
-        if (c * 64 >= m) continue;  // (uniform over the wave)
-        const int i = c * 64 + lane;
-        const int64_t row = i < m ? (int64_t)surv[(int64_t)q * rs + i] : -1;
-        const float raw = wave_exact_any<METRIC, DIRECT>(p, q, row, tile);
-        if (i < m) recs[(int64_t)q * rs + i] = rerank_rec<METRIC>(p, row, raw);
-    }
-}
-
-bool launch_rerank_ids_wide(const ScanParams &p, int metric, const int64_t *cand, int ncand, int k,
-                            int64_t id_offset, int64_t *out_ids, float *out_dist, const RerankPrune &pr,
-                            uint32_t *surv, int *cnt, uint4 *recs, hipStream_t s) {
-    if (ncand > kSortCap || (p.d & 3) || p.nq <= 0) return false;
-    const bool direct = !blas_formula(p);
-    const int chunks = (ncand + 63) / 64;
-    const int64_t items = (int64_t)p.nq * chunks;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((items + 3) / 4, 8192));
-    int rcap = 1;  // (every query holds at most ncand records: LDS for that many)
-    while (rcap < ncand) rcap <<= 1;
-#define MQVS_RW(M)                                                                                                  \
-    do {                                                                                                            \
-        hipLaunchKernelGGL((k_rerank_plan<M>), dim3((p.nq + 3) / 4), dim3(256), 0, s, p, cand, ncand, k, pr, surv,  \
-                           cnt);                                                                                    \
-        if (direct)                                                                                                 \
-            hipLaunchKernelGGL((k_exact_records_w<M, true>), dim3(grid), dim3(SEL_THREADS), 0, s, p, surv, cnt,      \
-                               (int64_t)ncand, chunks, recs);                                                       \
-        else                                                                                                        \
-            hipLaunchKernelGGL((k_exact_records_w<M, false>), dim3(grid), dim3(SEL_THREADS), 0, s, p, surv, cnt,     \
-                               (int64_t)ncand, chunks, recs);                                                       \
-        hipLaunchKernelGGL((k_sort_emit<M>), dim3(p.nq), dim3(SEL_THREADS), (rcap + kSelCap) * sizeof(uint4), s,     \
-                           recs, cnt, (int64_t)ncand, k, id_offset, out_ids, out_dist, rcap, nullptr, nullptr);     \
-    } while (0)
-    switch (metric) {
-        case MQVS_METRIC_L2: MQVS_RW(MQVS_METRIC_L2); break;
-        case MQVS_METRIC_IP: MQVS_RW(MQVS_METRIC_IP); break;
-        default: MQVS_RW(MQVS_METRIC_COSINE); break;
-    }
-#undef MQVS_RW
-    return true;
-}
-
 template <int M, bool DIRECT>
 static void rerank_ids_t(const ScanParams &p, const int64_t *cand, int ncand, int k, int64_t id_offset,
                          int64_t *ids, float *dist, uint4 *scratch, hipStream_t s, const RerankPrune &pr) {
     int N = 1;
     while (N < ncand) N <<= 1;
     if (scratch) N = kSortCap;  // LDS records of global_sort
-    if ((p.d & 3) == 0 && !scratch && ncand <= kRrPairMax && tune_int("MQVS_RR_PAIR", 0) == 1) {
-        const size_t lds = 2 * (size_t)ncand * sizeof(uint4) + (SEL_THREADS / 64) * 64 * kRrStride * sizeof(float);
-        hipLaunchKernelGGL((k_rerank_ids_pair<M, DIRECT>), dim3((p.nq + 1) / 2), dim3(SEL_THREADS), lds, s, p, cand,
-                           ncand, k, id_offset, ids, dist, pr);
-    } else if ((p.d & 3) == 0) {
+    if ((p.d & 3) == 0) {
         const size_t lds = N * sizeof(uint4) + (SEL_THREADS / 64) * 64 * kRrStride * sizeof(float);
-        // (measurement build A/B: MQVS_IDX_XPF=3, the query slice three tiles ahead)
-        if (tune_int("MQVS_IDX_XPF", 1) == 3)
-            hipLaunchKernelGGL((k_rerank_ids_tiled<M, DIRECT, 3>), dim3(p.nq), dim3(SEL_THREADS), lds, s, p, cand,
-                               ncand, k, id_offset, ids, dist, N, scratch, pr);
-        else
-            hipLaunchKernelGGL((k_rerank_ids_tiled<M, DIRECT>), dim3(p.nq), dim3(SEL_THREADS), lds, s, p, cand,
-                               ncand, k, id_offset, ids, dist, N, scratch, pr);
+        hipLaunchKernelGGL((k_rerank_ids_tiled<M, DIRECT>), dim3(p.nq), dim3(SEL_THREADS), lds, s, p, cand, ncand, k,
+                           id_offset, ids, dist, N, scratch, pr);
     } else {
         hipLaunchKernelGGL((k_rerank_ids<M, DIRECT>), dim3(p.nq), dim3(SEL_THREADS), N * sizeof(uint4), s, p, cand,
                            ncand, k, id_offset, ids, dist, scratch, pr);

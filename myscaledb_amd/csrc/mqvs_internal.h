@@ -270,12 +270,6 @@ struct RerankPrune {
 void launch_rerank_ids(const ScanParams &p, int metric, const int64_t *cand, int ncand, int k,
                        int64_t id_offset, int64_t *out_ids, float *out_dist, uint4 *scratch, hipStream_t s,
                        const RerankPrune &prune = RerankPrune{});
-// the same re-rank over waves (k_rerank_plan + k_exact_records_w +
-// k_sort_emit; ncand <= kSortCap, d % 4 == 0, else false and nothing runs):
-// scratch surv [nq][ncand] u32, cnt [nq], recs [nq][ncand]
-bool launch_rerank_ids_wide(const ScanParams &p, int metric, const int64_t *cand, int ncand, int k,
-                            int64_t id_offset, int64_t *out_ids, float *out_dist, const RerankPrune &pr,
-                            uint32_t *surv, int *cnt, uint4 *recs, hipStream_t s);
 void launch_scan_mfma(const ScanParams &p, int metric, bool probe, hipStream_t s);
 void launch_probe_select(const float *probe, int64_t P, int64_t ld, int nq, int k, int metric,
                          uint32_t *tau, int *cand_count, Cand *cand, int cand_cap,
@@ -468,7 +462,7 @@ struct IvfParams {
     int64_t *qstart;          // [nq+1] start of each query's region
     Cand *cand;               // approximate values, one per (pair, list position)
     int64_t *stats;           // [4] values written, items, plane bytes, pairs
-    int64_t *bsum;            // [3 * plan workgroups] per-workgroup list totals (k_plan_lists_reg)
+    int64_t *bsum;            // [3 * plan workgroups] per-workgroup list totals (k_plan_lists_blk)
     // pair mode (pair_stride > 0; few pairs per list): no plan -- work item
     // it is (pair it / pair_nch, slice it % pair_nch) of one query, query q's
     // region starts at q * pair_stride and holds its probes' lists back to back
@@ -535,7 +529,7 @@ bool timing_on(uint32_t flags);
 // (pq: a's words are the sums over npq rows of pq[npq][na] instead)
 void launch_words_to_host(const int64_t *a, int na, const int *b, int nb, int64_t *host_a, int *host_b,
                           hipStream_t s, const int64_t *pq = nullptr, int npq = 0);
-bool launch_scan_p4_groups(const ScanParams &p, int metric, int grp, hipStream_t s);
+bool launch_scan_p4_groups(const ScanParams &p, int metric, hipStream_t s);
 void launch_centroid_mean(const float *rows, int d, const int32_t *order, const int64_t *off, int nlist, float *cent,
                           hipStream_t s);
 

@@ -290,8 +290,8 @@ def test_index_torch_device_pointers(mq):
 
 
 def test_index_many_lists(mq):
-    """More than 16384 lists (the strided plan kernel, k_plan_lists, and the
-    FLAT coarse step): the returned rows carry their exact distances and the
+    """More than 16384 lists (the multi-workgroup plan kernel, k_plan_lists_blk,
+    and the FLAT coarse step): the returned rows carry their exact distances and the
     recall against FLAT is high when many lists are probed."""
     n, d, nq, k, nlist = 60000, 32, 50, 10, 20000
     seg = mq.VectorScanSegment.generate(0x5EED0001, 2, n, d, metric="L2")

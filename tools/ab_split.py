@@ -4,7 +4,8 @@
 each split, with the ids / distances of every split compared bit for bit to
 the exact path (mqvs_set_batch_mode(1): fp32 MFMA for nq >= 20, the exact VALU
 scan below).  One JSON line per (split, metric, mode, nq).
-Env overrides per arm: --tunes 'MQVS_HI_TUNE=2,4,4;MQVS_HI_TUNE=2,4,3'."""
+Env overrides per arm (the switches of csrc/tuning.h; with --dbg):
+--tunes 'MQVS_HI_PP=2;MQVS_HI_PP=0'."""
 import argparse
 import json
 import os
@@ -26,7 +27,7 @@ def main():
     ap.add_argument("--metrics", default="Cosine")
     ap.add_argument("--modes", default="2")
     ap.add_argument("--splits", default="2,6")
-    ap.add_argument("--tunes", default="", help="';'-separated ENV=VALUE settings, each its own arm")
+    ap.add_argument("--tunes", default="", help="';'-separated ENV=VALUE settings (csrc/tuning.h), each its own arm")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sels", default="", help="PREWHERE selectivities in percent (attr < T over a uniform attr "
                                                "in [0, 100), the configs[4] shape); empty: no filter")
