@@ -72,7 +72,9 @@ enum {
                                    valid once the stream drains AND
                                    mqvs_async_check returns MQVS_OK: a search
                                    that would have needed a host-driven
-                                   fallback (candidate overflow, cosine variant
+                                   fallback (candidate overflow, a query whose
+                                   norm is NaN, infinite or >= 1e18 on a
+                                   pre-filtered segment, cosine variant
                                    check) is reported there as
                                    MQVS_ERR_LOGICAL and must be repeated
                                    without ASYNC */

@@ -475,6 +475,13 @@ static mqvs_index *build_impl(mqvs_segment *seg, const char *index_type, const c
             assign_rows(ix, ix->cent, seg->rows, n, assign.as<int64_t>(), adist.as<float>(), s);
             MQVS_HIP(hipMemcpyAsync(ha.data(), assign.p, sizeof(int64_t) * n, hipMemcpyDeviceToHost, s));
             MQVS_HIP(hipStreamSynchronize(s));
+            // a row no centroid can take (NaN components; an infinite one
+            // whose product with every centroid is -inf or NaN) comes back
+            // as -1: list 0 holds it, so every non-empty row is in a list
+            // and a search of every list sees what FLAT sees (such a row can
+            // still be a result: +inf under IP for a query of the other sign)
+            for (int64_t &a : ha)
+                if (a < 0 || a >= Lc) a = 0;
         }
         group_by_list(ha, Lc, kIvfPad, order, off, keep.empty() ? nullptr : &keep);
         ix->npos = off[Lc];
@@ -1003,7 +1010,15 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
     // and more of them only score more centroids exactly,
     // profiles/r05/pick/core_t_ab.jsonl)
     float *qrec0 = nullptr;  // variant 0's norm records (the pick's bound; the re-rank pruning's)
-    if (cmode == 2 && nprobe <= kCoarsePickMaxT && ix->cent && ix->cent->rows_hi && ix->cent->rows) {
+    if (nprobe >= ix->nlist) {
+        // every list is probed: nothing to rank, and nothing to lose -- the
+        // ranked forms never pick a centroid whose score is NaN (a NaN or
+        // infinite query; a centroid of a list that holds infinite rows)
+        launch_iota_probes(probes, nq, nprobe, s);
+        MQVS_HIP(hipGetLastError());
+        picked = true;
+    }
+    if (!picked && cmode == 2 && nprobe <= kCoarsePickMaxT && ix->cent && ix->cent->rows_hi && ix->cent->rows) {
         mqvs_segment *cs = ix->cent;
         const int64_t vpad = rup(nq, 16);
         auto *cq = (uint16_t *)ws.cqhi.get(sizeof(uint16_t) * (size_t)vpad * cs->dpad);
@@ -1043,7 +1058,7 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
             float *cbq = (float *)ws.cbq.get(sizeof(float) * (size_t)nq);
             ScanParams bp = cp;
             bp.blas_nq = 1;
-            launch_query_bound(bp, ix->coarse_metric, cs->ynorm_max, crec, cs->ynorm_max + 4, cbq, s);
+            launch_query_bound(bp, ix->coarse_metric, cs->ynorm_max, crec, cs->ynorm_max + 4, cbq, nullptr, s);
             MQVS_HIP(hipGetLastError());
             launch_coarse_pick(cp.p4_gmax, gld, 32 * cp.tiles, nprobe, nprobe, ix->coarse_metric, qvars,
                                (int64_t)maxv * qstride, cs->rows, cs->norms, cs->n, d, cbq, qnorms, 3, nq, probes,
@@ -1090,7 +1105,7 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
         bp.maxv = 1;
         bp.qnorms = qnorms;
         bp.blas_nq = fnq;
-        launch_query_bound(bp, ix->metric, seg->ynorm_max, qrec0, ix->yrec, ibq, s);
+        launch_query_bound(bp, ix->metric, seg->ynorm_max, qrec0, ix->yrec, ibq, nullptr, s);
         MQVS_HIP(hipGetLastError());
     }
     if (split) fork_chain();

@@ -88,13 +88,21 @@ void launch_max_norm(const float *norms2, int64_t n, float *out_max, hipStream_t
 //   approximation with fl(sum (y-x)^2), so add the norms' rounding (d u each)
 //   and the direct sum's own error ((d+3) u (|x|+|y|)^2 <= 2 (d+3) u top):
 //   2 B + (3 d + 12) u top.
+//
+// The bound holds for finite arithmetic.  Rows are limited by the segment
+// (approx_ok: |y| < 1e18); a query of norm 1e18 or more (or NaN) can overflow
+// the approximate sum where the exact chain does not (all-1e30 query over rows
+// of scale 1e17: the MFMA sum meets +inf and -inf, NaN, and a NaN passes no
+// threshold, while the fma chain of the BLAS formula stays at +inf, a valid
+// IP): such a query sets bit 4 of *flags and the exact path serves the search.
 __global__ void k_query_bound(ScanParams p, int metric, int direct, const float *ynorm_max, const float *qrec,
-                              const float *yrec, float *bq) {
+                              const float *yrec, float *bq, int *flags) {
     // one thread per query (|x| from the variants' norm records)
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= p.nq) return;
     const int nv = p.maxv <= 1 ? 1 : p.qmu[j] + p.qlam[j];
     float xmax = 0.f;
+    bool big = false;
     const float ymax = *ynorm_max * (1.0f + 6e-8f * (float)p.d + 1e-6f);  // fp32 |y|^2 chain error
     const float du = (float)p.d * 5.9604645e-8f;
     float b;
@@ -110,6 +118,7 @@ __global__ void k_query_bound(ScanParams p, int metric, int direct, const float 
         for (int v = 0; v < nv; ++v) {
             const float *q = qrec + ((int64_t)j * p.maxv + v) * kMxRec;
             xmax = fmaxf(xmax, q[6]);
+            big |= !(q[6] < 1e18f);  // (NaN included, which fmaxf drops)
             const float trunc = q[0] * Y[1] + q[1] * Y[0] + q[1] * Y[1];
             const float bv = trunc + 2.04f * du * q[0] * Y[0] + 1.01f * du * q[6] * ymax + 1.2e-7f * q[6] * ymax;
             b = fmaxf(b, bv * 1.0001f);
@@ -129,12 +138,13 @@ __global__ void k_query_bound(ScanParams p, int metric, int direct, const float 
     }
     if (!(b < 1e30f)) b = __builtin_inff();
     bq[j] = b;
+    if (flags && big) atomicOr(flags, 4);
 }
 
 void launch_query_bound(const ScanParams &p, int metric, const float *ynorm_max, const float *qrec,
-                        const float *yrec, float *bq, hipStream_t s) {
+                        const float *yrec, float *bq, int *flags, hipStream_t s) {
     const int direct = !blas_formula(p);
-    hipLaunchKernelGGL(k_query_bound, dim3((unsigned)((p.nq + 255) / 256)), dim3(256), 0, s, p, metric, direct, ynorm_max, qrec, yrec, bq);
+    hipLaunchKernelGGL(k_query_bound, dim3((unsigned)((p.nq + 255) / 256)), dim3(256), 0, s, p, metric, direct, ynorm_max, qrec, yrec, bq, flags);
 }
 
 

@@ -615,9 +615,16 @@ __global__ __launch_bounds__(NT) void k_ivf_select(const Cand *cand, IvfRegions 
     ivf_region(rg, q, rs0, T);
     ivf_pair_stats(rg, q, T, threadIdx.x == 0);
     const Cand *c = cand + rs0;
+    // A row whose approximate value is NaN (an infinite component, or
+    // products that overflow to both infinities in the MFMA sum) can still
+    // have a valid exact value (the fma chain of the BLAS formula stays at
+    // the first infinity): before a re-rank it ranks first (key 0, below
+    // every value's key) and the exact value decides; a first-stage-only
+    // search has no exact value to give and leaves it out.
+    const uint32_t nan_key = out_approx ? 0xFFFFFFFFu : 0u;
     auto gkey = [&](int64_t i) {
         const Cand e = c[i];
-        return e.row == 0xFFFFFFFFu ? 0xFFFFFFFFu : okey<METRIC>(e.raw);
+        return e.row == 0xFFFFFFFFu ? 0xFFFFFFFFu : e.raw != e.raw ? nan_key : okey<METRIC>(e.raw);
     };
     const bool cached = T <= keycap;
     if (t == 0) {

@@ -118,8 +118,9 @@ __device__ inline void rerank_emit(uint4 *recs, uint4 *g, int ncand, int k, int 
 // (L2; at least a_k - B for IP / cosine, larger better); a candidate with a >
 // a_k + 2B has an exact value strictly worse, and so has every later one.
 // The output is the same as re-ranking all of them.  No pruning (m = ncand)
-// when a_k is not a valid value, B is not finite, or for IP the k best could
-// fall under the FLT_MIN cut (searchWrapper's init) and leave fewer than k.
+// when a_k or the first value is not a number, B is not finite, or for IP the
+// k best could fall under the FLT_MIN cut (searchWrapper's init) and leave
+// fewer than k.
 // wave_prune_cut: the cut of query q, computed by one wave (its 64 lanes
 // share the cosine variant distances); returns whether pruning applies and
 // the cut w on the approximate raw value (keep a <= w for L2, a >= w else),
@@ -150,10 +151,13 @@ __device__ inline bool wave_prune_cut(const ScanParams &p, const RerankPrune &pr
         }
     }
     const float ak = pr.raw[(int64_t)q * ncand + k - 1];
+    // (candidates whose approximate value is NaN sort first, k_ivf_select:
+    // the bound says nothing about them, so their presence turns pruning off)
+    const float a0 = pr.raw[(int64_t)q * ncand];
     const float ym = *pr.ymax;
     const float dv = dmax > 0.0 ? (float)(sqrt(dmax) * (1.0 + 1e-6)) * ym * 1.0001f : 0.f;
     const float b = pr.bq[q] + dv + 1e-30f;
-    bool ok = ak == ak && b < 1e30f && ym < 1e30f;
+    bool ok = ak == ak && a0 == a0 && b < 1e30f && ym < 1e30f;
     if (METRIC == MQVS_METRIC_L2) {
         w = ak + 2.0f * b;
         w = w + fabsf(w) * 2.4e-7f + 1e-30f;

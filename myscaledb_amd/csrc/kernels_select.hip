@@ -113,9 +113,24 @@ __global__ __launch_bounds__(SEL_THREADS) void k_final_select(const Cand *cand,
         // rows tying at the k-th key rank by row (L2 / IP / binary: the key
         // then the row is the whole order), so when more than kSortCap rows
         // reach the k-th key only the smallest rows of the tie are kept (the
-        // (k - #below)-th smallest tied row bounds them); cosine ties also
-        // rank by chunk and ip and keep the plain path
-        uint32_t rth = 0xFFFFFFFFu;
+        // (k - #below)-th smallest tied row bounds them); cosine ties rank by
+        // (chunk, ip descending, row): their cut (yth, zth, rth) is found
+        // below, only once the plain gather has overflowed
+        uint32_t rth = 0xFFFFFFFFu, yth = 0xFFFFFFFFu, zth = 0xFFFFFFFFu;
+        auto chunk_of = [&](const Cand &e) { return chunk_rows > 0 ? (uint32_t)((int64_t)e.row / chunk_rows) : 0u; };
+        // block-wide count of the candidates that pass pred
+        auto count_if = [&](auto pred) {
+            __syncthreads();
+            if (threadIdx.x == 0) s_cnt = 0;
+            __syncthreads();
+            int mine = 0;
+            for (int i = threadIdx.x; i < n; i += SEL_THREADS) mine += pred(c[i]) ? 1 : 0;
+            if (mine) atomicAdd(&s_cnt, mine);
+            __syncthreads();
+            const int total = s_cnt;
+            __syncthreads();
+            return total;
+        };
         if (METRIC != MQVS_METRIC_COSINE && th != 0xFFFFFFFEu) {
             if (threadIdx.x == 0) s_cnt = 0;
             __syncthreads();
@@ -143,20 +158,43 @@ __global__ __launch_bounds__(SEL_THREADS) void k_final_select(const Cand *cand,
                 rth = block_radix_select(rowof, n, k - nbelow, hist, sh);
             }
         }
-        if (threadIdx.x == 0) s_cnt = 0;
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += SEL_THREADS) {
-            const Cand e = c[i];
-            const uint32_t key = key32<METRIC>(e.raw);
-            if (key != 0xFFFFFFFFu && (key < th || (key == th && e.row <= rth))) {
-                const int pos = atomicAdd(&s_cnt, 1);
-                const uint4 r = make_rec(e);
-                if (pos < kSortCap) recs[pos] = r;
-                if (g && pos < kLargeCap) g[pos] = r;
+        auto tie_kept = [&](const Cand &e) {
+            if (METRIC != MQVS_METRIC_COSINE) return e.row <= rth;
+            if (yth == 0xFFFFFFFFu) return true;  // (no cut)
+            const uint32_t y = chunk_of(e), z = ~ord_asc(e.raw);
+            return y < yth || (y == yth && (z < zth || (z == zth && e.row <= rth)));
+        };
+        for (int pass = 0;; ++pass) {
+            if (threadIdx.x == 0) s_cnt = 0;
+            __syncthreads();
+            for (int i = threadIdx.x; i < n; i += SEL_THREADS) {
+                const Cand e = c[i];
+                const uint32_t key = key32<METRIC>(e.raw);
+                if (key != 0xFFFFFFFFu && (key < th || (key == th && tie_kept(e)))) {
+                    const int pos = atomicAdd(&s_cnt, 1);
+                    const uint4 r = make_rec(e);
+                    if (pos < kSortCap) recs[pos] = r;
+                    if (g && pos < kLargeCap) g[pos] = r;
+                }
             }
+            __syncthreads();
+            m = s_cnt;
+            if (METRIC != MQVS_METRIC_COSINE || pass > 0 || m <= lcap || th == 0xFFFFFFFEu) break;
+            // cosine, more than lcap rows up to the k-th 1-ip (rows that skip
+            // the normalisation, or zero rows, all at distance 1): the
+            // (k - #below)-th tied row in (chunk, ip descending, row) order,
+            // one radix select per level, and the gather again: exactly k
+            auto tied = [&](const Cand &e) { return key32<METRIC>(e.raw) == th; };
+            int kk = k - count_if([&](const Cand &e) { return key32<METRIC>(e.raw) < th; });
+            yth = block_radix_select([&](int64_t i) { return tied(c[i]) ? chunk_of(c[i]) : 0xFFFFFFFFu; }, n, kk, hist, sh);
+            kk -= count_if([&](const Cand &e) { return tied(e) && chunk_of(e) < yth; });
+            auto in_y = [&](const Cand &e) { return tied(e) && chunk_of(e) == yth; };
+            zth = block_radix_select([&](int64_t i) { return in_y(c[i]) ? ~ord_asc(c[i].raw) : 0xFFFFFFFFu; }, n, kk, hist, sh);
+            kk -= count_if([&](const Cand &e) { return in_y(e) && ~ord_asc(e.raw) < zth; });
+            rth = block_radix_select(
+                [&](int64_t i) { return in_y(c[i]) && ~ord_asc(c[i].raw) == zth ? c[i].row : 0xFFFFFFFFu; }, n, kk, hist, sh);
+            __syncthreads();
         }
-        __syncthreads();
-        m = s_cnt;
         if (m > lcap) {  // more than lcap rows tie at the k-th key
             if (threadIdx.x == 0) atomicOr(overflow, 2);
             m = lcap;

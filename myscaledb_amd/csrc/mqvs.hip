@@ -1167,7 +1167,7 @@ static void search_impl(mqvs_segment *seg, const float *queries, int nq, int k, 
             launch_to_hi(qvars, nvec, d, qstride, seg->dpad, maxv, vpad, qhi, qrec, nullptr, s);
             p.q_vpad = vpad;
             p.q_hi = qhi;
-            launch_query_bound(p, metric, seg->ynorm_max, qrec, seg->ynorm_max + 4, bq, s);
+            launch_query_bound(p, metric, seg->ynorm_max, qrec, seg->ynorm_max + 4, bq, overflow, s);
             // cosine batches: a chunk's query variants as one contiguous plane
             // (kernels_p4.hip; up to 32 planes within the scratch budget; the
             // scan keeps per-query variant reads when the chains need more)
@@ -2599,7 +2599,8 @@ int mqvs_async_check(mqvs_stream_t stream) {
         MQVS_HIP(hipMemcpy(&word, ws.sticky.p, sizeof(int), hipMemcpyDeviceToHost));
         MQVS_HIP(hipMemset(ws.sticky.p, 0, 16));
         if (word & 1)
-            fail(MQVS_ERR_LOGICAL, "an ASYNC search needed its candidate-overflow fallback (results invalid): "
+            fail(MQVS_ERR_LOGICAL, "an ASYNC search needed its exact fallback (candidate overflow, or a query "
+                                   "whose norm is NaN, infinite or at least 1e18; results invalid): "
                                    "repeat it without MQVS_F_ASYNC");
         if (word & 2)
             fail(MQVS_ERR_LOGICAL, "an ASYNC cosine search's query normalisation did not repeat within " +

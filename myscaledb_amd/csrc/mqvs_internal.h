@@ -387,8 +387,11 @@ void launch_to_bf16(const float *src, int64_t rows, int d, int64_t src_stride, u
                     hipStream_t s);
 void launch_max_norm(const float *norms2, int64_t n, float *out_max, hipStream_t s);
 // qrec [nq][maxv][kMxRec] query-variant norm records, yrec [kMxRec] segment maxima
+// flags (may be null): the search's overflow word; bit 4 (as k_survivors':
+// the exact path must serve the search) is set for a query whose norm is NaN
+// or at least 1e18
 void launch_query_bound(const ScanParams &p, int metric, const float *ynorm_max, const float *qrec,
-                        const float *yrec, float *bq, hipStream_t s);
+                        const float *yrec, float *bq, int *flags, hipStream_t s);
 // split 2 (kernels_hi.hip): row-blocked bf16 hi plane (16 vectors x 32
 // columns contiguous; source vector v goes to plane vector
 // (v % vgroup) vpad + v / vgroup) + records [|h|, |r|, -, -, -, -, |x|] per

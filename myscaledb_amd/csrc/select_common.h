@@ -438,15 +438,21 @@ __device__ inline float okey_bound_value(uint32_t k) {
     return METRIC == MQVS_METRIC_L2 ? __builtin_inff() : -__builtin_inff();
 }
 
-// threshold on the approximate value that keeps every row of the exact top-k
+// threshold on the approximate value that keeps every row of the exact top-k.
+// An infinite k-th value makes the arithmetic inf - inf (IP / cosine with
+// kth = +inf: t - |t| 2.4e-7, or t itself under an infinite bound; L2 with
+// kth = -inf): a threshold that is not a number keeps every row -- a NaN
+// would fail every row's test and keep none.
 template <int METRIC>
 __device__ inline float widen(float kth, float b) {
     if (METRIC == MQVS_METRIC_L2) {
         const float t = kth + 2.0f * b;
-        return t + fabsf(t) * 2.4e-7f + 1e-30f;
+        const float w = t + fabsf(t) * 2.4e-7f + 1e-30f;
+        return w == w ? w : __builtin_inff();
     }
     const float t = kth - 2.0f * b;
-    return t - fabsf(t) * 2.4e-7f - 1e-30f;
+    const float w = t - fabsf(t) * 2.4e-7f - 1e-30f;
+    return w == w ? w : -__builtin_inff();
 }
 
 
