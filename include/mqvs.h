@@ -485,6 +485,99 @@ int mqvs_index_search_binary(mqvs_index_t idx, const uint8_t *queries, int32_t n
 int mqvs_index_centroids_binary(mqvs_index_t idx, uint8_t *out, int64_t cap_bytes);
 int mqvs_index_probes_binary(mqvs_index_t idx, const uint8_t *queries, int32_t nq, const char *params,
                              int64_t *out_probes);
+
+/* ---- index persistence: save a built index, load it without a build ---------
+ * The reference keeps index files in the part directory and loads them on a
+ * cache miss (VIWithColumnInPart::serialize / ::load, VIWithDataPart.cpp:578-764;
+ * VICacheManager).  A built index is determined by the segment's resident rows
+ * plus five things -- the centroid table, each row's list, nlist, alpha, np95
+ * -- and only those are saved: about 4 n + 4 nlist dim bytes.  The bf16 plane
+ * and every other derived array is rebuilt by the load, which runs no k-means
+ * and no search of rows against centroids.
+ *
+ * The blob is one ClickHouse CompressedWriteBuffer stream, the framing
+ * mqvs_segment_create_from_column reads.  Each block:
+ *   bytes 0-15   CityHash128 v1.0.2 of bytes 16 .. 24 + payload (low word first)
+ *   byte  16     method: 0x02 NONE (what mqvs_index_save writes) or 0x82 LZ4
+ *   bytes 17-20  UInt32 compressed size = payload bytes + 9
+ *   bytes 21-24  UInt32 decompressed size
+ *   bytes 25-    payload
+ * mqvs_index_save writes NONE blocks of at most 1 MiB of payload;
+ * mqvs_index_load reads any chain the column ingest reads, LZ4 included, so
+ * the file may be re-compressed.  The decompressed content, little-endian:
+ *   bytes 0-7    magic "MQVSIDX\0"
+ *   bytes 8-11   UInt32 format version (MQVS_INDEX_BLOB_VERSION = 1)
+ *   bytes 12-15  UInt32 kind: 0 float IVF, 1 binary IVF (MQVS_INDEX_KIND_*)
+ *   bytes 16-19  UInt32 metric (mqvs_metric: the index's search metric)
+ *   bytes 20-23  UInt32 dimension: dim for float, dim_bits for binary
+ *   bytes 24-31  UInt64 n, the segment's rows
+ *   bytes 32-39  UInt64 nlist
+ *   bytes 40-43  alpha, the default search alpha, as fp32 bits
+ *   bytes 44-47  UInt32 np95 (0: not measured; see mqvs_index_build)
+ *   bytes 48-55  UInt64 fingerprint of the segment's resident rows (below)
+ *   bytes 56-63  reserved, zero
+ *   bytes 64-    the centroid table: nlist x dim fp32 as mqvs_index_centroids
+ *                returns it (float), nlist x dim_bits / 8 bytes as
+ *                mqvs_index_centroids_binary returns it (binary)
+ *   then         the assignment: n Int32, each row's list id, or -1 for a row
+ *                in no list (an empty array; float only).  A row the build
+ *                forced into list 0 is stored as 0.
+ * Nothing in it depends on the kernels' layouts (list padding, plane tiling).
+ * Not saved: the row-ids map of a decoupled part (the reference keeps it in
+ * the part's own files: register it again with mqvs_index_set_row_ids_map
+ * after the load), the bf16 plane, any derived state.
+ *
+ * Fingerprint: S = min(n, 1024) rows, row floor(i n / S) for i < S, back to
+ * back -- a float row as its dim fp32 values as resident (normalised on a
+ * cosine segment), a binary row as its dim_bits / 8 bytes -- taken as the
+ * payload of one method-NONE block; the fingerprint is the low 64 bits of the
+ * checksum that block would carry (CityHash128 over its 9 header bytes +
+ * payload).  It is computed on the device from the resident rows, in HBM or
+ * in host memory (mqvs_segment_set_rows_host).
+ *
+ * mqvs_index_save_size: the exact size of the blob.  mqvs_index_save: the blob
+ *   into the host buffer out[cap]; cap too small -> MQVS_ERR_BAD_ARGUMENTS.
+ * mqvs_index_load: the index of `blob` over `seg`, as mqvs_index_build returns
+ *   it: mqvs_index_info reports the built index's nlist, npos, max_list,
+ *   rows_indexed, metric, dim and hbm_bytes (build_ms: the load's device
+ *   time), and searches return the built index's bits.  Every check happens
+ *   before any blob content is used:
+ *     truncated or malformed block chain, bad magic or header field, a
+ *     decompressed size other than the header implies, an assignment value
+ *     outside [-1, nlist), a binary assignment of -1   MQVS_ERR_ILLEGAL_COLUMN
+ *     a block checksum mismatch                         MQVS_ERR_CHECKSUM
+ *     unknown format version                            MQVS_ERR_NOT_IMPLEMENTED
+ *     float blob on a binary segment or the reverse; n, dimension or cosine /
+ *     non-cosine family other than the segment's; fingerprint mismatch
+ *                                                       MQVS_ERR_LOGICAL
+ *     dimension over the list scan's limit              MQVS_ERR_BAD_ARGUMENTS
+ * mqvs_index_blob_info: host only, no device call: the header fields of a
+ *   blob whose first block is stored with method NONE; an LZ4 first block ->
+ *   MQVS_ERR_NOT_IMPLEMENTED.  For system tables and tooling.
+ * mqvs_index_lists: introspection, as mqvs_index_centroids: list_off[nlist + 1]
+ *   and the part row of every position (-1 = padding) in position order. */
+#define MQVS_INDEX_BLOB_VERSION 1
+#define MQVS_INDEX_BLOB_HEADER_BYTES 64
+#define MQVS_INDEX_KIND_FLOAT_IVF 0
+#define MQVS_INDEX_KIND_BINARY_IVF 1
+typedef struct {
+    uint32_t version;
+    uint32_t kind;         /* MQVS_INDEX_KIND_* */
+    int32_t metric;
+    int32_t dim;           /* dim, or dim_bits for binary */
+    int64_t n;
+    int64_t nlist;
+    float alpha;
+    int32_t np95;
+    uint64_t fingerprint;
+    uint64_t content_bytes; /* decompressed size the header implies */
+} mqvs_index_blob_info_t;
+int mqvs_index_save_size(mqvs_index_t idx, size_t *bytes);
+int mqvs_index_save(mqvs_index_t idx, uint8_t *out, size_t cap, size_t *written);
+int mqvs_index_load(mqvs_segment_t seg, const uint8_t *blob, size_t bytes, mqvs_index_t *out);
+int mqvs_index_blob_info(const uint8_t *blob, size_t bytes, mqvs_index_blob_info_t *out);
+int mqvs_index_lists(mqvs_index_t idx, int64_t *list_off, int64_t cap_off, int32_t *rows, int64_t cap_rows);
+
 /* Decoupled parts: a part merged from several source parts whose index still
  * serves the source part's rows (the reference's VIWithMeta row_ids_map /
  * inverted maps, VICacheObject.h:50-64).

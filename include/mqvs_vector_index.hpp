@@ -477,6 +477,31 @@ public:
         part.rerank(queries, nq, local.data(), ncand, top_k, row_exists, ids, dist);
     }
 
+    /// VIWithColumnInPart::serialize (VIWithDataPart.cpp:578-764): the index as
+    /// one byte string for the part directory (include/mqvs.h: index
+    /// persistence).  A row-ids map is not part of it.
+    std::vector<uint8_t> serialize() const
+    {
+        size_t bytes = 0, written = 0;
+        check(mqvs_index_save_size(idx->h, &bytes));
+        std::vector<uint8_t> blob(bytes);
+        check(mqvs_index_save(idx->h, blob.data(), blob.size(), &written));
+        blob.resize(written);
+        return blob;
+    }
+
+    /// VIWithColumnInPart::load: the index of a serialize()d byte string over
+    /// the resident part it was built on, without a build.  Throws as
+    /// mqvs_index_load reports (a blob of another part: LOGICAL_ERROR).
+    static GpuIndex load(const PartScan & part, const uint8_t * data, size_t size)
+    {
+        mqvs_index_t h = nullptr;
+        check(mqvs_index_load(part.handle(), data, size, &h));
+        GpuIndex out(part, h);
+        out.idx->owned = true;
+        return out;
+    }
+
     /// VIWithMeta::row_ids_map of a decoupled part (source row -> new row);
     /// an empty map clears it.
     void setRowIdsMap(const std::vector<uint64_t> & row_ids_map) const
@@ -611,6 +636,31 @@ public:
                                                 0u, nullptr);
         checkOrFallback(st, static_cast<bool>(fallback),
                         [&] { fallback(queries, nq, k, params, filter, row_exists, ids, dist); });
+    }
+
+    /// VIWithColumnInPart::serialize (VIWithDataPart.cpp:578-764): the index as
+    /// one byte string for the part directory (include/mqvs.h: index
+    /// persistence).  A row-ids map is not part of it.
+    std::vector<uint8_t> serialize() const
+    {
+        size_t bytes = 0, written = 0;
+        check(mqvs_index_save_size(idx->h, &bytes));
+        std::vector<uint8_t> blob(bytes);
+        check(mqvs_index_save(idx->h, blob.data(), blob.size(), &written));
+        blob.resize(written);
+        return blob;
+    }
+
+    /// VIWithColumnInPart::load: the index of a serialize()d byte string over
+    /// the resident part it was built on, without a build.  Throws as
+    /// mqvs_index_load reports (a blob of another part: LOGICAL_ERROR).
+    static BinaryGpuIndex load(const BinaryPartScan & part, const uint8_t * data, size_t size)
+    {
+        mqvs_index_t h = nullptr;
+        check(mqvs_index_load(part.handle(), data, size, &h));
+        BinaryGpuIndex out(part, h);
+        out.idx->owned = true;
+        return out;
     }
 
     /// VIWithMeta::row_ids_map of a decoupled part (source row -> new row);

@@ -16,7 +16,7 @@ from .vector_scan import (  # noqa: F401
     try_brute_force_search_binary,
     vector_scan_without_index,
 )
-from .vector_index import BinaryVectorIndex, VectorIndex  # noqa: F401
+from .vector_index import BinaryVectorIndex, VectorIndex, index_blob_info  # noqa: F401
 
-__all__ = ["BinaryVectorScanSegment", "try_brute_force_search_binary", "VectorScanSegment", "init", "merge_shards", "pack_bitmap",
+__all__ = ["index_blob_info","BinaryVectorScanSegment", "try_brute_force_search_binary", "VectorScanSegment", "init", "merge_shards", "pack_bitmap",
            "try_brute_force_search", "vector_scan_without_index", "VectorIndex", "BinaryVectorIndex"]

@@ -51,6 +51,7 @@ SYMBOLS = [
     "mqvs_index_build", "mqvs_index_free", "mqvs_index_info", "mqvs_index_search", "mqvs_index_last_stats",
     "mqvs_index_centroids", "mqvs_index_probes",
     "mqvs_index_search_binary", "mqvs_index_centroids_binary", "mqvs_index_probes_binary",
+    "mqvs_index_save_size", "mqvs_index_save", "mqvs_index_load", "mqvs_index_blob_info", "mqvs_index_lists",
     "mqvs_segment_create_binary", "mqvs_search_binary", "mqvs_knn_binary_raw",
     "mqvs_segment_create_from_column", "mqvs_async_check",
     "mqvs_comm_unique_id", "mqvs_comm_init", "mqvs_comm_init_loopback", "mqvs_comm_free", "mqvs_sharded_search", "mqvs_comm_stats",
@@ -78,6 +79,13 @@ class IndexInfo(ctypes.Structure):
     _fields_ = [("nlist", ctypes.c_int64), ("npos", ctypes.c_int64), ("max_list", ctypes.c_int64),
                 ("rows_indexed", ctypes.c_int64), ("metric", ctypes.c_int32), ("dim", ctypes.c_int32),
                 ("hbm_bytes", ctypes.c_size_t), ("build_ms", ctypes.c_double)]
+
+
+class IndexBlobInfo(ctypes.Structure):
+    _fields_ = [("version", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("metric", ctypes.c_int32),
+                ("dim", ctypes.c_int32), ("n", ctypes.c_int64), ("nlist", ctypes.c_int64),
+                ("alpha", ctypes.c_float), ("np95", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
+                ("content_bytes", ctypes.c_uint64)]
 
 
 class CacheStats(ctypes.Structure):
@@ -168,6 +176,11 @@ def _load(path=LIB_PATH):
         "mqvs_index_search_binary": ([P, P, I32, I32, ctypes.c_char_p, P, P, P, P, U32, P], ctypes.c_int),
         "mqvs_index_centroids_binary": ([P, P, I64], ctypes.c_int),
         "mqvs_index_probes_binary": ([P, P, I32, ctypes.c_char_p, P], ctypes.c_int),
+        "mqvs_index_save_size": ([P, P], ctypes.c_int),
+        "mqvs_index_save": ([P, P, ctypes.c_size_t, P], ctypes.c_int),
+        "mqvs_index_load": ([P, P, ctypes.c_size_t, P], ctypes.c_int),
+        "mqvs_index_blob_info": ([P, ctypes.c_size_t, P], ctypes.c_int),
+        "mqvs_index_lists": ([P, P, I64, P, I64], ctypes.c_int),
         "mqvs_segment_create_binary": ([P, I64, I32, I32, I64, I64, U32, P], ctypes.c_int),
         "mqvs_search_binary": ([P, P, I32, I32, I32, P, P, P, P, U32, P], ctypes.c_int),
         "mqvs_knn_binary_raw": ([P, P, I64, I64, I64, I64, I32, P, P], ctypes.c_int),

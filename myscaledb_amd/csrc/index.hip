@@ -9,13 +9,15 @@
 // The MSTG library itself is absent from the snapshot, so the
 // structure below is this library's own design for HBM and MFMA:
 //
-// Build (all on the GPU except two counting sorts on the host):
+// Build (all on the GPU except the sample's counting sort per k-means step):
 //   k-means over a row sample: assignment = FLAT top-1 search of the sample
 //   rows against a centroid segment (the MFMA pre-filter path of mqvs_search),
 //   deterministic ordered means (k_centroid_mean); cosine centroids are
 //   re-normalised (spherical k-means).  Every row is then assigned to its
-//   nearest centroid, rows are grouped by list (stable: row order within a
-//   list), and the lists are written back to back as a bf16 plane.
+//   nearest centroid; finish_index groups the rows by list on the device (row
+//   order within a list) and writes the lists back to back as a bf16 plane.
+// Save / load (mqvs_index_save, mqvs_index_load): centroids + each row's list
+//   behind a 64-byte header; the load ends in the same finish_index.
 // Search:
 //   coarse   FLAT search of the queries against the centroid segment, k =
 //            nprobe (L2 for L2 parts, raw inner product for IP and cosine)
@@ -260,13 +262,14 @@ static void assign_rows(mqvs_index *ix, mqvs_segment *cseg, const float *rows, i
 }
 
 // stable counting sort of assign[m] (list ids, -1 dropped): order (indices
-// into the assigned set, ascending within a list) and offsets [L+1]
+// into the assigned set, ascending within a list) and offsets [L+1] (the
+// k-means steps over the sample; the rows themselves: finish_index)
 static void group_by_list(const std::vector<int64_t> &assign, int64_t L, int64_t pad, std::vector<int32_t> &order,
-                          std::vector<int64_t> &off, const std::vector<uint8_t> *keep) {
+                          std::vector<int64_t> &off) {
     std::vector<int64_t> cnt(L + 1, 0);
     for (size_t i = 0; i < assign.size(); ++i) {
         const int64_t a = assign[i];
-        if (a >= 0 && a < L && (!keep || (*keep)[i])) ++cnt[a];
+        if (a >= 0 && a < L) ++cnt[a];
     }
     off.assign(L + 1, 0);
     for (int64_t l = 0; l < L; ++l) off[l + 1] = off[l] + rup(cnt[l], pad);
@@ -274,7 +277,7 @@ static void group_by_list(const std::vector<int64_t> &assign, int64_t L, int64_t
     std::vector<int64_t> cur(off.begin(), off.end() - 1);
     for (size_t i = 0; i < assign.size(); ++i) {
         const int64_t a = assign[i];
-        if (a >= 0 && a < L && (!keep || (*keep)[i])) order[cur[a]++] = (int32_t)i;
+        if (a >= 0 && a < L) order[cur[a]++] = (int32_t)i;
     }
 }
 
@@ -329,6 +332,109 @@ constexpr int64_t kAutoNlistMinRows = 1 << 20;  // smaller parts take the defaul
 
 static mqvs_index *build_binary_impl(mqvs_segment *seg, const char *params);
 
+// the list scan keeps a tile of at least 16 bf16 queries in LDS
+// (ivf_scan_lds): rows too wide for that cannot be searched
+static void check_index_width(mqvs_segment *seg) {
+    const int d = seg->d;
+    DeviceGuard guard(seg->device);
+    const int64_t lim = device_lds_bytes();
+    if (ivf_fit_qg(16, rup(d, kBfK), lim) == 0) {
+        int64_t dmax = (lim / 16 - 32) / 2 / kBfK * kBfK;
+        fail(MQVS_ERR_BAD_ARGUMENTS, "dimension " + std::to_string(d) + " is too wide for an index: the list scan's " +
+                                         "16-query tile must fit the workgroup's " + std::to_string(lim) +
+                                         " bytes of LDS (at most " + std::to_string(dmax) + " dimensions)");
+    }
+}
+
+// ---- the tail of every build and of mqvs_index_load ---------------------------
+// From the centroids (ix->cent for a float index, ix->bcent for a binary one)
+// and the canonical assignment -- assign[n] on the device: each row's list, -1
+// for a row in no list -- to the finished index: the rows grouped by list on
+// the device (kernels_ivf.hip: k_grp_*), then everything derived from that:
+// the bf16 plane and |y|^2 in list order, the plane's norm maxima and the
+// coarse quantizer's centroid lists (float), or the codes in list order
+// (binary).  ix: seg, binary, metric, nlist, dpad set.  The assignment is
+// range-checked by the kernel that first reads it, and the verdict is read
+// before anything is sized by or indexed with it: from a blob (from_blob) a
+// bad value is the blob's fault, from a build the device's.
+static void finish_index(mqvs_index *ix, const int32_t *assign, bool from_blob, hipStream_t s) {
+    mqvs_segment *seg = ix->seg;
+    const int64_t n = seg->n, L = ix->nlist;
+    const int d = seg->d;
+    const uint8_t *nonempty = ix->binary ? nullptr : seg->nonempty_bits;
+    TmpBuf cnt(sizeof(int) * L), fill(sizeof(int) * L), info(sizeof(int64_t) * 8);
+    MQVS_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int) * L, s));
+    MQVS_HIP(hipMemsetAsync(fill.p, 0, sizeof(int) * L, s));
+    MQVS_HIP(hipMemsetAsync(info.p, 0, sizeof(int64_t) * 8, s));
+    int *status = (int *)(info.as<int64_t>() + 6);
+    ix->list_off = dalloc<int64_t>(ix, L + 1);
+    launch_grp_count(assign, n, L, nonempty, !ix->binary, cnt.as<int>(), status, s);
+    launch_grp_scan(cnt.as<int>(), L, ix->binary ? 1 : kIvfPad, ix->list_off, info.as<int64_t>(), status, s);
+    MQVS_HIP(hipGetLastError());
+    int64_t h[5] = {};
+    MQVS_HIP(hipMemcpyAsync(h, info.p, sizeof(h), hipMemcpyDeviceToHost, s));
+    MQVS_HIP(hipStreamSynchronize(s));
+    if (h[4]) {
+        const char *what = (h[4] & kGrpStatusBadRange) ? "a list id outside [-1, nlist)" : "a row of a binary index in no list";
+        fail(from_blob ? MQVS_ERR_ILLEGAL_COLUMN : MQVS_ERR_DEVICE,
+             std::string(from_blob ? "index blob: the assignment holds " : "index build: the assignment holds ") + what);
+    }
+    ix->npos = h[0];
+    ix->max_list = h[1];
+    ix->rows_indexed = h[2];
+    ix->perm = dalloc<int32_t>(ix, ix->npos);
+    {
+        const int64_t max_rows = h[3];
+        TmpBuf tmp(max_rows > kSortCap ? sizeof(int32_t) * (size_t)ix->npos : 0);
+        if (ix->npos > 0) MQVS_HIP(hipMemsetAsync(ix->perm, 0xFF, sizeof(int32_t) * (size_t)ix->npos, s));
+        launch_grp_scatter(assign, n, L, nonempty, ix->list_off, fill.as<int>(), ix->perm, s);
+        const int32_t *sorted = launch_grp_sort(ix->perm, tmp.as<int32_t>(), ix->list_off, cnt.as<int>(), L, ix->npos,
+                                                max_rows, s);
+        MQVS_HIP(hipGetLastError());
+        if (sorted != ix->perm)
+            MQVS_HIP(hipMemcpyAsync(ix->perm, sorted, sizeof(int32_t) * (size_t)ix->npos, hipMemcpyDeviceToDevice, s));
+        MQVS_HIP(hipStreamSynchronize(s));  // (tmp)
+    }
+    if (ix->binary) {
+        ix->bplane = dalloc<uint32_t>(ix, (size_t)ix->npos * seg->code_words);
+        launch_bivf_gather(seg->codes, seg->code_words, ix->perm, ix->npos, ix->bplane, s);
+        MQVS_HIP(hipGetLastError());
+        return;
+    }
+    ix->plane = dalloc<uint16_t>(ix, (size_t)ix->npos * ix->dpad);
+    ix->pnorm = dalloc<float>(ix, ix->npos);
+    launch_ivf_pack(seg->rows, seg->norms, d, ix->perm, ix->npos, ix->dpad, ix->plane, ix->pnorm, s);
+    MQVS_HIP(hipGetLastError());
+    // the plane's norm maxima (the same bf16 rounding as k_ivf_pack; empty
+    // arrays' FLT_MAX rows make them infinite, which turns the re-rank's
+    // bound pruning off)
+    ix->yrec = dalloc<float>(ix, kMxRec);
+    MQVS_HIP(hipMemsetAsync(ix->yrec, 0, sizeof(float) * kMxRec, s));
+    launch_to_hi(seg->rows, n, d, d, ix->dpad, 1, rup(n, 16), nullptr, nullptr, ix->yrec, s);
+    MQVS_HIP(hipGetLastError());
+    // ---- coarse quantizer as lists of kCoarseChunk centroids
+    ix->cnl = (L + kCoarseChunk - 1) / kCoarseChunk;
+    std::vector<int64_t> coff(ix->cnl + 1, 0);
+    std::vector<int32_t> cperm;
+    for (int64_t j = 0; j < ix->cnl; ++j) {
+        const int64_t b = j * kCoarseChunk, e = std::min(L, b + kCoarseChunk);
+        for (int64_t c = b; c < e; ++c) cperm.push_back((int32_t)c);
+        while ((int64_t)cperm.size() % kIvfPad) cperm.push_back(-1);
+        coff[j + 1] = (int64_t)cperm.size();
+        ix->cmax = std::max(ix->cmax, coff[j + 1] - coff[j]);
+    }
+    ix->cnpos = (int64_t)cperm.size();
+    ix->cperm = dalloc<int32_t>(ix, ix->cnpos);
+    ix->clist_off = dalloc<int64_t>(ix, ix->cnl + 1);
+    ix->cplane = dalloc<uint16_t>(ix, (size_t)ix->cnpos * ix->dpad);
+    ix->cpnorm = dalloc<float>(ix, ix->cnpos);
+    MQVS_HIP(hipMemcpyAsync(ix->cperm, cperm.data(), sizeof(int32_t) * ix->cnpos, hipMemcpyHostToDevice, s));
+    MQVS_HIP(hipMemcpyAsync(ix->clist_off, coff.data(), sizeof(int64_t) * (ix->cnl + 1), hipMemcpyHostToDevice, s));
+    launch_ivf_pack(ix->cent->rows, ix->cent->norms, d, ix->cperm, ix->cnpos, ix->dpad, ix->cplane, ix->cpnorm, s);
+    MQVS_HIP(hipGetLastError());
+    MQVS_HIP(hipStreamSynchronize(s));  // cperm / coff are host temporaries
+}
+
 static mqvs_index *build_impl(mqvs_segment *seg, const char *index_type, const char *params) {
     if (!seg) fail(MQVS_ERR_BAD_ARGUMENTS, "null segment");
     std::string type = index_type ? index_type : (seg->binary ? "BINARYMSTG" : "MSTG");
@@ -360,18 +466,7 @@ static mqvs_index *build_impl(mqvs_segment *seg, const char *index_type, const c
     }
     const int64_t n = seg->n;
     const int d = seg->d;
-    {
-        // the list scan keeps a tile of at least 16 bf16 queries in LDS
-        // (ivf_scan_lds): rows too wide for that cannot be searched
-        DeviceGuard guard(seg->device);
-        const int64_t lim = device_lds_bytes();
-        if (ivf_fit_qg(16, rup(d, kBfK), lim) == 0) {
-            int64_t dmax = (lim / 16 - 32) / 2 / kBfK * kBfK;
-            fail(MQVS_ERR_BAD_ARGUMENTS, "dimension " + std::to_string(d) + " is too wide for an index: the list scan's " +
-                                             "16-query tile must fit the workgroup's " + std::to_string(lim) +
-                                             " bytes of LDS (at most " + std::to_string(dmax) + " dimensions)");
-        }
-    }
+    check_index_width(seg);
     if (!pm.count("nlist") && n >= kAutoNlistMinRows && !seg->nonempty_bits) return build_auto(seg, index_type, params);
     // lists of about 256 rows (at most 65536 lists): fine enough that data of
     // many small clusters (generator mode 3: 65536 centres of ~150 rows)
@@ -456,7 +551,7 @@ static mqvs_index *build_impl(mqvs_segment *seg, const char *index_type, const c
             ha.resize(Sm);
             MQVS_HIP(hipMemcpyAsync(ha.data(), assign.p, sizeof(int64_t) * Sm, hipMemcpyDeviceToHost, s));
             MQVS_HIP(hipStreamSynchronize(s));
-            group_by_list(ha, Lc, 1, order, off, nullptr);
+            group_by_list(ha, Lc, 1, order, off);
             TmpBuf dord(sizeof(int32_t) * std::max<size_t>(order.size(), 1));
             TmpBuf doff(sizeof(int64_t) * off.size());
             if (!order.empty())
@@ -470,67 +565,17 @@ static mqvs_index *build_impl(mqvs_segment *seg, const char *index_type, const c
         ix->cent = segment_from_device(cent.as<float>(), Lc, d, cseg_metric, s);
 
         // ---- every row to its nearest centroid; lists in row order
-        ha.assign(n, 0);
-        if (Lc > 1 && n > 0) {
-            assign_rows(ix, ix->cent, seg->rows, n, assign.as<int64_t>(), adist.as<float>(), s);
-            MQVS_HIP(hipMemcpyAsync(ha.data(), assign.p, sizeof(int64_t) * n, hipMemcpyDeviceToHost, s));
-            MQVS_HIP(hipStreamSynchronize(s));
-            // a row no centroid can take (NaN components; an infinite one
-            // whose product with every centroid is -inf or NaN) comes back
-            // as -1: list 0 holds it, so every non-empty row is in a list
-            // and a search of every list sees what FLAT sees (such a row can
-            // still be a result: +inf under IP for a query of the other sign)
-            for (int64_t &a : ha)
-                if (a < 0 || a >= Lc) a = 0;
-        }
-        group_by_list(ha, Lc, kIvfPad, order, off, keep.empty() ? nullptr : &keep);
-        ix->npos = off[Lc];
-        ix->rows_indexed = 0;
-        for (int64_t l = 0; l < Lc; ++l) {
-            int64_t len = 0;
-            for (int64_t pos = off[l]; pos < off[l + 1]; ++pos) len += order[pos] >= 0;
-            ix->rows_indexed += len;
-            ix->max_list = std::max(ix->max_list, off[l + 1] - off[l]);
-        }
-        ix->perm = dalloc<int32_t>(ix, ix->npos);
-        ix->list_off = dalloc<int64_t>(ix, Lc + 1);
-        ix->plane = dalloc<uint16_t>(ix, (size_t)ix->npos * ix->dpad);
-        ix->pnorm = dalloc<float>(ix, ix->npos);
-        if (ix->npos > 0)
-            MQVS_HIP(hipMemcpyAsync(ix->perm, order.data(), sizeof(int32_t) * ix->npos, hipMemcpyHostToDevice, s));
-        MQVS_HIP(hipMemcpyAsync(ix->list_off, off.data(), sizeof(int64_t) * (Lc + 1), hipMemcpyHostToDevice, s));
-        launch_ivf_pack(seg->rows, seg->norms, d, ix->perm, ix->npos, ix->dpad, ix->plane, ix->pnorm, s);
+        // a row no centroid can take (NaN components; an infinite one
+        // whose product with every centroid is -inf or NaN) comes back
+        // as -1: list 0 holds it, so every non-empty row is in a list
+        // and a search of every list sees what FLAT sees (such a row can
+        // still be a result: +inf under IP for a query of the other sign)
+        TmpBuf canon(sizeof(int32_t) * std::max<int64_t>(n, 1));
+        const bool assigned = Lc > 1 && n > 0;
+        if (assigned) assign_rows(ix, ix->cent, seg->rows, n, assign.as<int64_t>(), adist.as<float>(), s);
+        launch_grp_canon(assigned ? assign.as<int64_t>() : nullptr, n, Lc, seg->nonempty_bits, canon.as<int32_t>(), s);
         MQVS_HIP(hipGetLastError());
-        // the plane's norm maxima (the same bf16 rounding as k_ivf_pack; empty
-        // arrays' FLT_MAX rows make them infinite, which turns the re-rank's
-        // bound pruning off)
-        ix->yrec = dalloc<float>(ix, kMxRec);
-        MQVS_HIP(hipMemsetAsync(ix->yrec, 0, sizeof(float) * kMxRec, s));
-        launch_to_hi(seg->rows, n, d, d, ix->dpad, 1, rup(n, 16), nullptr, nullptr, ix->yrec, s);
-        MQVS_HIP(hipGetLastError());
-        // ---- coarse quantizer as lists of kCoarseChunk centroids
-        {
-            ix->cnl = (Lc + kCoarseChunk - 1) / kCoarseChunk;
-            std::vector<int64_t> coff(ix->cnl + 1, 0);
-            std::vector<int32_t> cperm;
-            for (int64_t j = 0; j < ix->cnl; ++j) {
-                const int64_t b = j * kCoarseChunk, e = std::min(Lc, b + kCoarseChunk);
-                for (int64_t c = b; c < e; ++c) cperm.push_back((int32_t)c);
-                while ((int64_t)cperm.size() % kIvfPad) cperm.push_back(-1);
-                coff[j + 1] = (int64_t)cperm.size();
-                ix->cmax = std::max(ix->cmax, coff[j + 1] - coff[j]);
-            }
-            ix->cnpos = (int64_t)cperm.size();
-            ix->cperm = dalloc<int32_t>(ix, ix->cnpos);
-            ix->clist_off = dalloc<int64_t>(ix, ix->cnl + 1);
-            ix->cplane = dalloc<uint16_t>(ix, (size_t)ix->cnpos * ix->dpad);
-            ix->cpnorm = dalloc<float>(ix, ix->cnpos);
-            MQVS_HIP(hipMemcpyAsync(ix->cperm, cperm.data(), sizeof(int32_t) * ix->cnpos, hipMemcpyHostToDevice, s));
-            MQVS_HIP(hipMemcpyAsync(ix->clist_off, coff.data(), sizeof(int64_t) * (ix->cnl + 1), hipMemcpyHostToDevice, s));
-            launch_ivf_pack(ix->cent->rows, ix->cent->norms, d, ix->cperm, ix->cnpos, ix->dpad, ix->cplane, ix->cpnorm, s);
-            MQVS_HIP(hipGetLastError());
-            MQVS_HIP(hipStreamSynchronize(s));  // cperm / coff are host temporaries
-        }
+        finish_index(ix, canon.as<int32_t>(), false, s);
         MQVS_HIP(hipEventRecord(e1, s));
         MQVS_HIP(hipStreamSynchronize(s));
         float ms = 0.f;
@@ -1303,38 +1348,12 @@ static mqvs_index *build_binary_impl(mqvs_segment *seg, const char *params) {
             }
             MQVS_HIP(hipStreamSynchronize(s));  // (sidx / init are host temporaries)
         }
-        // ---- every row to its nearest centroid; lists in row order (a stable
-        // counting sort on the host)
-        std::vector<int32_t> ha(n);
+        // ---- every row to its nearest centroid; lists in row order
         if (n > 0) {
             launch_bivf_assign(seg->codes, n, cw, ix->bcent, (int)L, assign.as<int32_t>(), s);
             MQVS_HIP(hipGetLastError());
-            MQVS_HIP(hipMemcpyAsync(ha.data(), assign.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-            MQVS_HIP(hipStreamSynchronize(s));
         }
-        std::vector<int64_t> off(L + 1, 0);
-        for (int64_t i = 0; i < n; ++i) {
-            if (ha[i] < 0 || ha[i] >= L) fail(MQVS_ERR_DEVICE, "binary index build: list id out of range");
-            ++off[ha[i] + 1];
-        }
-        for (int64_t l = 0; l < L; ++l) {
-            ix->max_list = std::max(ix->max_list, off[l + 1]);
-            off[l + 1] += off[l];
-        }
-        std::vector<int32_t> order(n);
-        {
-            std::vector<int64_t> cur(off.begin(), off.end() - 1);
-            for (int64_t i = 0; i < n; ++i) order[cur[ha[i]]++] = (int32_t)i;
-        }
-        ix->npos = n;
-        ix->rows_indexed = n;
-        ix->perm = dalloc<int32_t>(ix, n);
-        ix->list_off = dalloc<int64_t>(ix, L + 1);
-        ix->bplane = dalloc<uint32_t>(ix, (size_t)n * cw);
-        if (n > 0) MQVS_HIP(hipMemcpyAsync(ix->perm, order.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-        MQVS_HIP(hipMemcpyAsync(ix->list_off, off.data(), sizeof(int64_t) * (L + 1), hipMemcpyHostToDevice, s));
-        launch_bivf_gather(seg->codes, cw, ix->perm, n, ix->bplane, s);
-        MQVS_HIP(hipGetLastError());
+        finish_index(ix, assign.as<int32_t>(), false, s);
         MQVS_HIP(hipEventRecord(e1, s));
         MQVS_HIP(hipStreamSynchronize(s));
         float ms = 0.f;
@@ -1537,6 +1556,315 @@ static void search_binary_index_impl(mqvs_index *ix, const uint8_t *queries, int
     g_istats = st;
 }
 
+// ---- persistence: mqvs_index_save / mqvs_index_load -------------------------
+// A saved index is the five things a build decides -- centroids, each row's
+// list, nlist, alpha, np95 -- behind a 64-byte header, framed as a ClickHouse
+// CompressedWriteBuffer stream (include/mqvs.h has the layout byte by byte).
+// Everything else is derived again by finish_index.  The framing reuses the
+// column ingest's device code in both directions: launch_block_table and
+// launch_decode_blocks read it, launch_block_checksum verifies it and, through
+// hash_out, computes the checksums the writer stores.
+
+constexpr int64_t kBlobBlock = 1 << 20;  // payload bytes of the blocks mqvs_index_save writes
+constexpr int64_t kBlobFrame = 25;       // 16-B checksum + method byte + two UInt32 sizes
+constexpr char kBlobMagic[8] = {'M', 'Q', 'V', 'S', 'I', 'D', 'X', '\0'};
+constexpr int kFingerprintRows = 1024;
+
+struct BlobHeader {  // little-endian, as the host is
+    char magic[8];
+    uint32_t version, kind, metric, dim;
+    uint64_t n, nlist;
+    uint32_t alpha_bits, np95;
+    uint64_t fingerprint;
+    uint8_t reserved[8];
+};
+static_assert(sizeof(BlobHeader) == MQVS_INDEX_BLOB_HEADER_BYTES, "the documented header");
+
+static void put_block_header(uint8_t *h, uint32_t payload) {  // h: the 9 bytes after the checksum
+    const uint32_t csize = payload + 9;
+    h[0] = 0x02;
+    for (int i = 0; i < 4; ++i) {
+        h[1 + i] = (uint8_t)(csize >> (8 * i));
+        h[5 + i] = (uint8_t)(payload >> (8 * i));
+    }
+}
+
+static int64_t row_bytes_of(const mqvs_segment *seg) { return seg->binary ? seg->code_bytes : 4 * (int64_t)seg->d; }
+
+// The fingerprint of a segment's resident rows: S = min(n, 1024) rows, row
+// floor(i n / S) for i < S (the builds' sample rule), gathered back to back (a
+// float row as its d fp32 values as they are resident -- normalised for a
+// cosine segment --, a binary row as its dim_bits / 8 code bytes) and framed as
+// the payload of one method-NONE block; the fingerprint is the low 64 bits of
+// that block's CityHash128 checksum (k_block_checksum, one lane).  The rows are
+// read through seg->rows / seg->codes, which for rows moved to host memory is
+// the mapped address of the pinned copy.
+static uint64_t segment_fingerprint(mqvs_segment *seg, hipStream_t s) {
+    const int64_t n = seg->n, S = std::min<int64_t>(n, kFingerprintRows), rb = row_bytes_of(seg);
+    const int64_t len = S * rb;
+    // the block starts at byte 7, so that its payload starts at byte 32
+    TmpBuf buf(32 + (size_t)len + 16), tab(sizeof(IngestBlock)), out(sizeof(uint64_t) * 2 + sizeof(int) * 2);
+    uint8_t pre[32] = {};
+    put_block_header(pre + 23, (uint32_t)len);
+    IngestBlock b{};
+    b.src = 32;
+    b.csize = b.usize = (uint32_t)len;
+    b.method = 0x02;
+    MQVS_HIP(hipMemcpyAsync(buf.p, pre, 32, hipMemcpyHostToDevice, s));
+    MQVS_HIP(hipMemcpyAsync(tab.p, &b, sizeof(b), hipMemcpyHostToDevice, s));
+    MQVS_HIP(hipMemsetAsync(out.p, 0, sizeof(uint64_t) * 2 + sizeof(int) * 2, s));
+    std::vector<int64_t> idx64(S);
+    std::vector<int32_t> idx32(S);
+    for (int64_t i = 0; i < S; ++i) idx32[i] = (int32_t)(idx64[i] = (int64_t)((__int128)i * n / S));
+    TmpBuf didx(sizeof(int64_t) * std::max<int64_t>(S, 1)), wide(seg->binary ? sizeof(uint32_t) * (size_t)S * seg->code_words : 0);
+    if (S > 0 && seg->binary) {
+        MQVS_HIP(hipMemcpyAsync(didx.p, idx32.data(), sizeof(int32_t) * S, hipMemcpyHostToDevice, s));
+        launch_bivf_gather(seg->codes, seg->code_words, didx.as<int32_t>(), S, wide.as<uint32_t>(), s);
+        MQVS_HIP(hipMemcpy2DAsync(buf.as<uint8_t>() + 32, (size_t)rb, wide.p, (size_t)seg->code_words * 4, (size_t)rb,
+                                  (size_t)S, hipMemcpyDeviceToDevice, s));
+    } else if (S > 0) {
+        MQVS_HIP(hipMemcpyAsync(didx.p, idx64.data(), sizeof(int64_t) * S, hipMemcpyHostToDevice, s));
+        launch_gather_rows(seg->rows, seg->d, seg->d, didx.as<int64_t>(), S, (float *)(buf.as<uint8_t>() + 32), s);
+    }
+    uint64_t *hash = out.as<uint64_t>();
+    launch_block_checksum(buf.as<uint8_t>(), tab.as<IngestBlock>(), 1, 1, (int *)(hash + 2), hash, s);
+    MQVS_HIP(hipGetLastError());
+    uint64_t h[2] = {};
+    MQVS_HIP(hipMemcpyAsync(h, hash, sizeof(h), hipMemcpyDeviceToHost, s));
+    MQVS_HIP(hipStreamSynchronize(s));
+    return h[0];
+}
+
+static int64_t blob_content_bytes(const mqvs_index *ix) {
+    return (int64_t)sizeof(BlobHeader) + ix->nlist * row_bytes_of(ix->seg) + 4 * ix->seg->n;
+}
+
+static size_t blob_bytes(const mqvs_index *ix) {
+    const int64_t content = blob_content_bytes(ix);
+    return (size_t)(content + kBlobFrame * ((content + kBlobBlock - 1) / kBlobBlock));
+}
+
+static size_t save_impl(mqvs_index *ix, uint8_t *out, size_t cap) {
+    if (!ix || !out) fail(MQVS_ERR_BAD_ARGUMENTS, "null argument");
+    mqvs_segment *seg = ix->seg;
+    const int64_t n = seg->n, L = ix->nlist, rb = row_bytes_of(seg), cb = L * rb;
+    const int64_t content = blob_content_bytes(ix), nb = (content + kBlobBlock - 1) / kBlobBlock;
+    const size_t total = blob_bytes(ix);
+    if (cap < total)
+        fail(MQVS_ERR_BAD_ARGUMENTS, "output holds " + std::to_string(cap) + " bytes, " + std::to_string(total) + " needed");
+    DeviceGuard guard(seg->device);
+    hipStream_t s = thread_stream(seg->device);
+    BlobHeader hd{};
+    std::memcpy(hd.magic, kBlobMagic, 8);
+    hd.version = MQVS_INDEX_BLOB_VERSION;
+    hd.kind = ix->binary ? MQVS_INDEX_KIND_BINARY_IVF : MQVS_INDEX_KIND_FLOAT_IVF;
+    hd.metric = (uint32_t)ix->metric;
+    hd.dim = (uint32_t)seg->d;
+    hd.n = (uint64_t)n;
+    hd.nlist = (uint64_t)L;
+    std::memcpy(&hd.alpha_bits, &ix->alpha, 4);
+    hd.np95 = (uint32_t)ix->np95;
+    hd.fingerprint = segment_fingerprint(seg, s);
+
+    // ---- the content: header, centroid table, canonical assignment
+    TmpBuf cont((size_t)content), asg(sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1));
+    uint8_t *c = cont.as<uint8_t>();
+    MQVS_HIP(hipMemcpyAsync(c, &hd, sizeof(hd), hipMemcpyHostToDevice, s));
+    if (ix->binary)
+        MQVS_HIP(hipMemcpy2DAsync(c + sizeof(hd), (size_t)rb, ix->bcent, (size_t)seg->code_words * 4, (size_t)rb,
+                                  (size_t)L, hipMemcpyDeviceToDevice, s));
+    else
+        MQVS_HIP(hipMemcpyAsync(c + sizeof(hd), ix->cent->rows, (size_t)cb, hipMemcpyDeviceToDevice, s));
+    if (n > 0) {
+        // the list of a position, scattered to its row; rows at no position: -1
+        MQVS_HIP(hipMemsetAsync(asg.p, 0xFF, sizeof(int32_t) * (size_t)n, s));
+        launch_grp_assign_of(ix->perm, ix->list_off, L, ix->npos, n, asg.as<int32_t>(), s);
+        MQVS_HIP(hipGetLastError());
+        MQVS_HIP(hipMemcpyAsync(c + sizeof(hd) + cb, asg.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    }
+    // ---- the frame: method NONE blocks of at most kBlobBlock bytes
+    TmpBuf framed(total), tab(sizeof(IngestBlock) * (size_t)nb), hashes(16 * (size_t)nb + 16);
+    std::vector<uint8_t> heads((size_t)nb * kBlobFrame, 0);
+    std::vector<IngestBlock> ht((size_t)nb);
+    for (int64_t i = 0; i < nb; ++i) {
+        const uint32_t len = (uint32_t)std::min(kBlobBlock, content - i * kBlobBlock);
+        put_block_header(heads.data() + i * kBlobFrame + 16, len);
+        ht[i].src = i * (kBlobBlock + kBlobFrame) + kBlobFrame;
+        ht[i].dst = i * kBlobBlock;
+        ht[i].csize = ht[i].usize = len;
+        ht[i].method = 0x02;
+        ht[i].pad = 0;
+    }
+    uint8_t *f = framed.as<uint8_t>();
+    const size_t pitch = (size_t)(kBlobBlock + kBlobFrame);
+    MQVS_HIP(hipMemcpy2DAsync(f, pitch, heads.data(), (size_t)kBlobFrame, (size_t)kBlobFrame, (size_t)nb,
+                              hipMemcpyHostToDevice, s));
+    const int64_t full = content / kBlobBlock, rest = content - full * kBlobBlock;
+    if (full > 0)
+        MQVS_HIP(hipMemcpy2DAsync(f + kBlobFrame, pitch, c, (size_t)kBlobBlock, (size_t)kBlobBlock, (size_t)full,
+                                  hipMemcpyDeviceToDevice, s));
+    if (rest > 0)
+        MQVS_HIP(hipMemcpyAsync(f + full * pitch + kBlobFrame, c + full * kBlobBlock, (size_t)rest,
+                                hipMemcpyDeviceToDevice, s));
+    MQVS_HIP(hipMemcpyAsync(tab.p, ht.data(), sizeof(IngestBlock) * (size_t)nb, hipMemcpyHostToDevice, s));
+    uint64_t *hash = hashes.as<uint64_t>();
+    // (the verdict word of the checksum pass is not read: the stored checksums are still zero)
+    launch_block_checksum(f, tab.as<IngestBlock>(), nb, 1, (int *)(hash + 2 * nb), hash, s);
+    MQVS_HIP(hipGetLastError());
+    MQVS_HIP(hipMemcpy2DAsync(f, pitch, hash, 16, 16, (size_t)nb, hipMemcpyDeviceToDevice, s));
+    MQVS_HIP(hipMemcpyAsync(out, f, total, hipMemcpyDeviceToHost, s));
+    MQVS_HIP(hipStreamSynchronize(s));
+    return total;
+}
+
+// the header of a decoded blob; throws what the error table of include/mqvs.h names
+static void check_blob_header(const BlobHeader &hd) {
+    if (std::memcmp(hd.magic, kBlobMagic, 8) != 0) fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: bad magic");
+    if (hd.version != MQVS_INDEX_BLOB_VERSION)
+        fail(MQVS_ERR_NOT_IMPLEMENTED, "index blob: format version " + std::to_string(hd.version) + " is not implemented");
+    float alpha;
+    std::memcpy(&alpha, &hd.alpha_bits, 4);
+    const bool fl = hd.kind == MQVS_INDEX_KIND_FLOAT_IVF, bi = hd.kind == MQVS_INDEX_KIND_BINARY_IVF;
+    const bool metric_ok = fl ? (hd.metric == MQVS_METRIC_L2 || hd.metric == MQVS_METRIC_IP || hd.metric == MQVS_METRIC_COSINE)
+                              : (hd.metric == MQVS_METRIC_HAMMING || hd.metric == MQVS_METRIC_JACCARD);
+    if ((!fl && !bi) || !metric_ok || hd.nlist < 1 || hd.nlist > (1u << 20) || hd.n >= ((uint64_t)1 << 31) ||
+        (hd.n > 0 && hd.nlist > hd.n) || !(alpha >= 1.0f && alpha <= 4.0f) || hd.np95 > (uint32_t)kSortCap ||
+        hd.dim == 0 || hd.dim > (1u << 24) || (bi && hd.dim % 8))
+        fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: malformed header");
+}
+
+static mqvs_index *load_impl(mqvs_segment *seg, const uint8_t *blob, size_t bytes) {
+    if (!seg || !blob) fail(MQVS_ERR_BAD_ARGUMENTS, "null argument");
+    if (bytes < (size_t)kBlobFrame + sizeof(BlobHeader)) fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: truncated");
+    const int64_t n = seg->n, rb = row_bytes_of(seg);
+    DeviceGuard guard(seg->device);
+    hipStream_t s = thread_stream(seg->device);
+    hipEvent_t e0, e1;
+    MQVS_HIP(hipEventCreate(&e0));
+    MQVS_HIP(hipEventCreate(&e1));
+    mqvs_index *ix = nullptr;
+    try {
+        MQVS_HIP(hipEventRecord(e0, s));
+        // ---- the block chain, its checksums, the decoded content
+        const int64_t maxb = (int64_t)bytes / kBlobFrame + 1;
+        TmpBuf dblob(bytes), tab(sizeof(IngestBlock) * (size_t)maxb), words(sizeof(int64_t) * 4);
+        MQVS_HIP(hipMemcpyAsync(dblob.p, blob, bytes, hipMemcpyHostToDevice, s));
+        launch_block_table(dblob.as<uint8_t>(), (int64_t)bytes, tab.as<IngestBlock>(), maxb, words.as<int64_t>(), s);
+        MQVS_HIP(hipGetLastError());
+        int64_t tb[3] = {};
+        MQVS_HIP(hipMemcpyAsync(tb, words.p, sizeof(tb), hipMemcpyDeviceToHost, s));
+        MQVS_HIP(hipStreamSynchronize(s));
+        // (no codec expands more than 256-fold: a larger claim is not allocated)
+        if (tb[2] || tb[1] < (int64_t)sizeof(BlobHeader) || tb[1] / 256 > (int64_t)bytes)
+            fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: truncated or malformed compressed block chain");
+        const int64_t nblk = tb[0], total = tb[1];
+        constexpr int kBadChecksum = 8;  // (the decode raises 4)
+        int *status = (int *)(words.as<int64_t>() + 3);
+        MQVS_HIP(hipMemsetAsync(status, 0, sizeof(int), s));
+        TmpBuf cont((size_t)total);
+        uint8_t *c = cont.as<uint8_t>();
+        launch_block_checksum(dblob.as<uint8_t>(), tab.as<IngestBlock>(), nblk, kBadChecksum, status, nullptr, s);
+        launch_decode_blocks(dblob.as<uint8_t>(), (int64_t)bytes, tab.as<IngestBlock>(), nblk, c, status, s);
+        MQVS_HIP(hipGetLastError());
+        int hstatus = 0;
+        BlobHeader hd{};
+        MQVS_HIP(hipMemcpyAsync(&hstatus, status, sizeof(int), hipMemcpyDeviceToHost, s));
+        MQVS_HIP(hipMemcpyAsync(&hd, c, sizeof(hd), hipMemcpyDeviceToHost, s));
+        MQVS_HIP(hipStreamSynchronize(s));
+        if (hstatus & kBadChecksum)
+            fail(MQVS_ERR_CHECKSUM, "Checksum doesn't match: corrupted data (index blob, CityHash128 of a compressed block)");
+        if (hstatus) fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: malformed LZ4 block (CANNOT_DECOMPRESS)");
+        // ---- the header against itself, then against the segment
+        check_blob_header(hd);
+        const bool binary = hd.kind == MQVS_INDEX_KIND_BINARY_IVF;
+        const int64_t L = (int64_t)hd.nlist;
+        const int64_t hrb = binary ? hd.dim / 8 : 4 * (int64_t)hd.dim, cb = L * hrb;
+        if (total != (int64_t)sizeof(BlobHeader) + cb + 4 * (int64_t)hd.n)
+            fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: " + std::to_string(total) + " bytes of content, the header implies " +
+                                              std::to_string((int64_t)sizeof(BlobHeader) + cb + 4 * (int64_t)hd.n));
+        if (binary != seg->binary)
+            fail(MQVS_ERR_LOGICAL, std::string("index blob: a ") + (binary ? "binary" : "Float32") + " index on a " +
+                                       (seg->binary ? "binary" : "Float32") + " segment");
+        if ((int64_t)hd.n != n || (int64_t)hd.dim != seg->d)
+            fail(MQVS_ERR_LOGICAL, "index blob: saved over " + std::to_string(hd.n) + " rows of dimension " +
+                                       std::to_string(hd.dim) + ", the segment has " + std::to_string(n) + " of " +
+                                       std::to_string(seg->d));
+        if (!binary && ((int)hd.metric == MQVS_METRIC_COSINE) != (seg->metric == MQVS_METRIC_COSINE))
+            fail(MQVS_ERR_LOGICAL, "segment was prepared for a different metric (cosine segments are normalised in HBM)");
+        if (!binary) check_index_width(seg);
+        if (hd.fingerprint != segment_fingerprint(seg, s))
+            fail(MQVS_ERR_LOGICAL, "index blob: saved over other rows than the segment's (fingerprint mismatch)");
+
+        // ---- the index
+        ix = new mqvs_index();
+        ix->seg = seg;
+        ix->binary = binary;
+        ix->metric = (int)hd.metric;
+        ix->nlist = L;
+        std::memcpy(&ix->alpha, &hd.alpha_bits, 4);
+        ix->np95 = (int)hd.np95;
+        if (binary) {
+            ix->coarse_metric = MQVS_METRIC_HAMMING;
+            const size_t cwb = (size_t)seg->code_words * 4;
+            ix->bcent = dalloc<uint32_t>(ix, (size_t)L * seg->code_words);
+            MQVS_HIP(hipMemsetAsync(ix->bcent, 0, cwb * (size_t)L, s));
+            MQVS_HIP(hipMemcpy2DAsync(ix->bcent, cwb, c + sizeof(hd), (size_t)rb, (size_t)rb, (size_t)L,
+                                      hipMemcpyDeviceToDevice, s));
+        } else {
+            ix->coarse_metric = ix->metric == MQVS_METRIC_L2 ? MQVS_METRIC_L2 : kMetricIpRaw;
+            ix->dpad = rup(seg->d, kBfK);
+            ix->cent = segment_from_device((const float *)(c + sizeof(hd)), L, seg->d,
+                                           ix->metric == MQVS_METRIC_L2 ? MQVS_METRIC_L2 : MQVS_METRIC_IP, s);
+        }
+        // (the assignment follows a binary centroid table at any byte offset)
+        TmpBuf asg(sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1));
+        if (n > 0)
+            MQVS_HIP(hipMemcpyAsync(asg.p, c + sizeof(hd) + cb, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
+        finish_index(ix, asg.as<int32_t>(), true, s);
+        MQVS_HIP(hipEventRecord(e1, s));
+        MQVS_HIP(hipStreamSynchronize(s));
+        float ms = 0.f;
+        MQVS_HIP(hipEventElapsedTime(&ms, e0, e1));
+        ix->build_ms = ms;
+        if (ix->cent) ix->bytes += ix->cent->bytes;
+    } catch (...) {
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        if (ix) free_index(ix);
+        throw;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return ix;
+}
+
+// host only: the header of a blob whose first block is stored (method NONE)
+static void blob_info_impl(const uint8_t *blob, size_t bytes, mqvs_index_blob_info_t *out) {
+    if (!blob || !out) fail(MQVS_ERR_BAD_ARGUMENTS, "null argument");
+    if (bytes < (size_t)kBlobFrame + sizeof(BlobHeader)) fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: truncated");
+    const uint8_t *h = blob + 16;
+    auto u32 = [](const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); };
+    if (h[0] == 0x82) fail(MQVS_ERR_NOT_IMPLEMENTED, "index blob: the first block is LZ4-compressed (load it, or decompress it first)");
+    const uint32_t csize = u32(h + 1), usize = u32(h + 5);
+    if (h[0] != 0x02 || csize < 9 || csize - 9 != usize || usize < sizeof(BlobHeader) || 16 + (size_t)csize > bytes)
+        fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: malformed first block");
+    BlobHeader hd;
+    std::memcpy(&hd, blob + kBlobFrame, sizeof(hd));
+    check_blob_header(hd);
+    std::memset(out, 0, sizeof(*out));
+    out->version = hd.version;
+    out->kind = hd.kind;
+    out->metric = (int32_t)hd.metric;
+    out->dim = (int32_t)hd.dim;
+    out->n = (int64_t)hd.n;
+    out->nlist = (int64_t)hd.nlist;
+    std::memcpy(&out->alpha, &hd.alpha_bits, 4);
+    out->np95 = (int32_t)hd.np95;
+    out->fingerprint = hd.fingerprint;
+    const int64_t hrb = hd.kind == MQVS_INDEX_KIND_BINARY_IVF ? hd.dim / 8 : 4 * (int64_t)hd.dim;
+    out->content_bytes = (uint64_t)((int64_t)sizeof(BlobHeader) + (int64_t)hd.nlist * hrb + 4 * (int64_t)hd.n);
+}
+
 }  // namespace mqvs
 
 using namespace mqvs;
@@ -1649,6 +1977,47 @@ int mqvs_index_probes_binary(mqvs_index_t idx, const uint8_t *queries, int32_t n
         std::vector<float> dd((size_t)nq);
         search_binary_index_impl(idx, queries, nq, 1, params, nullptr, nullptr, ids.data(), dd.data(), 0, nullptr,
                                  out_probes);
+    });
+}
+
+int mqvs_index_save_size(mqvs_index_t idx, size_t *bytes) {
+    return guarded([&] {
+        if (!idx || !bytes) fail(MQVS_ERR_BAD_ARGUMENTS, "null argument");
+        *bytes = blob_bytes(idx);
+    });
+}
+
+int mqvs_index_save(mqvs_index_t idx, uint8_t *out, size_t cap, size_t *written) {
+    return guarded([&] {
+        if (written) *written = 0;
+        const size_t w = save_impl(idx, out, cap);
+        if (written) *written = w;
+    });
+}
+
+int mqvs_index_load(mqvs_segment_t seg, const uint8_t *blob, size_t bytes, mqvs_index_t *out) {
+    return guarded([&] {
+        if (!out) fail(MQVS_ERR_BAD_ARGUMENTS, "null output handle");
+        *out = nullptr;
+        *out = load_impl(seg, blob, bytes);
+    });
+}
+
+int mqvs_index_blob_info(const uint8_t *blob, size_t bytes, mqvs_index_blob_info_t *out) {
+    return guarded([&] { blob_info_impl(blob, bytes, out); });
+}
+
+int mqvs_index_lists(mqvs_index_t idx, int64_t *list_off, int64_t cap_off, int32_t *rows, int64_t cap_rows) {
+    return guarded([&] {
+        if (!idx || !list_off || (idx->npos > 0 && !rows)) fail(MQVS_ERR_BAD_ARGUMENTS, "null argument");
+        if (cap_off < idx->nlist + 1 || cap_rows < idx->npos)
+            fail(MQVS_ERR_BAD_ARGUMENTS, "outputs hold " + std::to_string(cap_off) + " offsets and " +
+                                             std::to_string(cap_rows) + " rows, " + std::to_string(idx->nlist + 1) +
+                                             " and " + std::to_string(idx->npos) + " needed");
+        DeviceGuard guard(idx->seg->device);
+        MQVS_HIP(hipMemcpy(list_off, idx->list_off, sizeof(int64_t) * (size_t)(idx->nlist + 1), hipMemcpyDeviceToHost));
+        if (idx->npos > 0)
+            MQVS_HIP(hipMemcpy(rows, idx->perm, sizeof(int32_t) * (size_t)idx->npos, hipMemcpyDeviceToHost));
     });
 }
 

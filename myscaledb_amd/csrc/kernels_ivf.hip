@@ -1419,4 +1419,266 @@ void launch_coarse_pick(const float *gmax, int64_t gld, int64_t ngroups, int T, 
 #undef MQVS_PICK
 }
 
+// ---------------------------------------------------------------------------
+// Rows grouped by list on the device (index.hip: finish_index, the tail of
+// both builds and of mqvs_index_load).  Input: the canonical assignment
+// assign[n] (list id, -1 = in no list).  Output: list_off[L + 1] with every
+// list's length rounded up to `pad`, and perm[npos]: position list_off[l] + j
+// holds the j-th smallest row of list l, every other position -1 -- what a
+// stable counting sort of the rows by list id gives.
+//   k_grp_count    range check of every value (status word, read by the host
+//                  before perm exists) + rows per list
+//   k_grp_scan     offsets, npos, longest list, rows in lists (one workgroup)
+//   k_grp_scatter  rows to their list's positions through atomic cursors: the
+//                  order within a list is whatever the atomics gave
+//   k_grp_sort     every run of kSortCap positions of a list sorted ascending
+//                  in LDS: lists up to kSortCap rows are then final
+//   k_grp_merge    longer lists: sorted runs merged pairwise through a second
+//                  buffer, doubling the run length per pass; an element's
+//                  place is its index in its run + the elements of the sibling
+//                  run below it (rows are distinct)
+// The result is a function of assign alone: the atomics only choose which
+// order the sort receives.
+
+// the wave's next slots of ctr[a] for its valid lanes: one atomic for the wave
+// when they all have the same list (one list holding every row would
+// serialise n atomics on one word), else one per lane.  Every lane of the
+// wave calls it.
+__device__ inline int grp_take(int *ctr, int32_t a, bool valid) {
+    const uint64_t m = __ballot(valid);
+    if (m == 0) return 0;
+    const int lane = threadIdx.x & 63;
+    const int first = __ffsll((long long)m) - 1;
+    const int32_t a0 = __shfl(a, first);
+    if (__ballot(valid && a == a0) == m) {
+        int base = 0;
+        if (lane == first) base = atomicAdd(&ctr[a0], (int)__popcll(m));
+        base = __shfl(base, first);
+        return base + (int)__popcll(m & ((1ull << lane) - 1ull));
+    }
+    return valid ? atomicAdd(&ctr[a], 1) : 0;
+}
+
+// (a row whose array is empty is in no list whatever the assignment says)
+__global__ __launch_bounds__(256) void k_grp_count(const int32_t *assign, int64_t n, int64_t L,
+                                                   const uint8_t *nonempty, int allow_none, int *cnt, int *status) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t base = blockIdx.x * 256ll + (threadIdx.x & ~63); base < n; base += (int64_t)gridDim.x * 256) {
+        const int64_t i = base + lane;
+        int32_t a = -1;
+        if (i < n) {
+            a = assign[i];
+            if (a < -1 || (int64_t)a >= L) {
+                atomicOr(status, kGrpStatusBadRange);
+                a = -1;
+            } else if (a < 0 && !allow_none) {
+                atomicOr(status, kGrpStatusNoList);
+            }
+            if (nonempty && !bit_test(nonempty, i)) a = -1;
+        }
+        (void)grp_take(cnt, a, a >= 0);
+    }
+}
+
+// info: [0] npos, [1] longest list in positions, [2] rows in lists, [3] rows of the longest list, [4] status
+__global__ __launch_bounds__(1024) void k_grp_scan(const int *cnt, int64_t L, int pad, int64_t *off, int64_t *info,
+                                                   const int *status) {
+    __shared__ int64_t s_sum[1024];
+    __shared__ unsigned long long s_red[3];
+    const int t = threadIdx.x;
+    if (t < 3) s_red[t] = 0;
+    const int64_t per = (L + 1023) / 1024;
+    const int64_t b = min(L, t * per), e = min(L, b + per);
+    int64_t sum = 0, mxp = 0, mxc = 0, rows = 0;
+    for (int64_t l = b; l < e; ++l) {
+        const int64_t c = cnt[l], p = (c + pad - 1) / pad * pad;
+        sum += p;
+        rows += c;
+        mxp = max(mxp, p);
+        mxc = max(mxc, c);
+    }
+    s_sum[t] = sum;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int64_t v = t >= o ? s_sum[t - o] : 0;
+        __syncthreads();
+        s_sum[t] += v;
+        __syncthreads();
+    }
+    atomicMax(&s_red[0], (unsigned long long)mxp);
+    atomicAdd(&s_red[1], (unsigned long long)rows);
+    atomicMax(&s_red[2], (unsigned long long)mxc);
+    int64_t run = s_sum[t] - sum;
+    for (int64_t l = b; l < e; ++l) {
+        off[l] = run;
+        run += ((int64_t)cnt[l] + pad - 1) / pad * pad;
+    }
+    __syncthreads();
+    if (t == 0) {
+        off[L] = s_sum[1023];
+        info[0] = s_sum[1023];
+        info[1] = (int64_t)s_red[0];
+        info[2] = (int64_t)s_red[1];
+        info[3] = (int64_t)s_red[2];
+        info[4] = *status;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_grp_scatter(const int32_t *assign, int64_t n, int64_t L,
+                                                     const uint8_t *nonempty, const int64_t *off, int *fill,
+                                                     int32_t *perm) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t base = blockIdx.x * 256ll + (threadIdx.x & ~63); base < n; base += (int64_t)gridDim.x * 256) {
+        const int64_t i = base + lane;
+        int32_t a = -1;
+        if (i < n) {
+            a = assign[i];
+            if (a < 0 || (int64_t)a >= L || (nonempty && !bit_test(nonempty, i))) a = -1;
+        }
+        const int j = grp_take(fill, a, a >= 0);
+        if (a >= 0) perm[off[a] + j] = (int32_t)i;
+    }
+}
+
+// blockIdx.x strides the lists, blockIdx.y a list's runs of kSortCap positions
+__global__ __launch_bounds__(256) void k_grp_sort(int32_t *perm, const int64_t *off, const int *cnt, int64_t L) {
+    __shared__ int32_t s_row[kSortCap];
+    const int t = threadIdx.x;
+    for (int64_t l = blockIdx.x; l < L; l += gridDim.x) {
+        const int64_t c = cnt[l];
+        if (c < 2) continue;
+        const int64_t p0 = off[l];
+        for (int64_t u0 = (int64_t)blockIdx.y * kSortCap; u0 < c; u0 += (int64_t)gridDim.y * kSortCap) {
+            const int len = (int)min((int64_t)kSortCap, c - u0);
+            int N = 2;
+            while (N < len) N <<= 1;
+            for (int i = t; i < N; i += 256) s_row[i] = i < len ? perm[p0 + u0 + i] : 0x7FFFFFFF;
+            __syncthreads();
+            for (int size = 2; size <= N; size <<= 1) {
+                for (int stride = size >> 1; stride > 0; stride >>= 1) {
+                    for (int i = t; i < (N >> 1); i += 256) {
+                        const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
+                        const int32_t x = s_row[lo], y = s_row[hi];
+                        if ((x > y) == ((lo & size) == 0)) {
+                            s_row[lo] = y;
+                            s_row[hi] = x;
+                        }
+                    }
+                    __syncthreads();
+                }
+            }
+            for (int i = t; i < len; i += 256) perm[p0 + u0 + i] = s_row[i];
+            __syncthreads();
+        }
+    }
+}
+
+// the list of position pos: the last l with off[l] <= pos (empty lists share
+// their successor's offset; pos < off[L])
+__device__ inline int64_t grp_list_of_pos(const int64_t *off, int64_t L, int64_t pos) {
+    int64_t lo = 0, hi = L - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= pos)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// one merge pass: sorted runs of `width` rows of every list longer than
+// kSortCap, src -> dst; every other position is copied
+__global__ __launch_bounds__(256) void k_grp_merge(const int32_t *src, int32_t *dst, const int64_t *off,
+                                                   const int *cnt, int64_t L, int64_t npos, int64_t width) {
+    for (int64_t pos = blockIdx.x * 256ll + threadIdx.x; pos < npos; pos += (int64_t)gridDim.x * 256) {
+        const int64_t l = grp_list_of_pos(off, L, pos);
+        const int64_t p0 = off[l], j = pos - p0, c = cnt[l];
+        const int32_t v = src[pos];
+        const int64_t a0 = j / (2 * width) * (2 * width), b0 = a0 + width;
+        if (c <= kSortCap || j >= c || b0 >= c) {
+            dst[pos] = v;
+            continue;
+        }
+        const bool in_a = j < b0;
+        // the sibling run, and how many of its rows are below v
+        const int32_t *sib = src + p0 + (in_a ? b0 : a0);
+        const int64_t sn = in_a ? min(width, c - b0) : width;
+        int64_t lo = 0, hi = sn;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (sib[mid] < v)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        dst[p0 + a0 + (j - (in_a ? a0 : b0)) + lo] = v;
+    }
+}
+
+// the canonical assignment of a built index: assign[perm[pos]] = list of pos
+// (assign filled with -1 by the caller)
+__global__ __launch_bounds__(256) void k_grp_assign_of(const int32_t *perm, const int64_t *off, int64_t L,
+                                                       int64_t npos, int64_t n, int32_t *assign) {
+    for (int64_t pos = blockIdx.x * 256ll + threadIdx.x; pos < npos; pos += (int64_t)gridDim.x * 256) {
+        const int32_t r = perm[pos];
+        if (r >= 0 && (int64_t)r < n) assign[r] = (int32_t)grp_list_of_pos(off, L, pos);
+    }
+}
+
+// a build's nearest-centroid ids as the canonical assignment: a row no
+// centroid took goes to list 0, a row with an empty array to no list
+__global__ __launch_bounds__(256) void k_grp_canon(const int64_t *assign, int64_t n, int64_t L,
+                                                   const uint8_t *nonempty, int32_t *out) {
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t a = assign ? assign[i] : 0;
+        out[i] = (nonempty && !bit_test(nonempty, i)) ? -1 : (a < 0 || a >= L) ? 0 : (int32_t)a;
+    }
+}
+
+static int grp_grid(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 65536); }
+
+void launch_grp_count(const int32_t *assign, int64_t n, int64_t L, const uint8_t *nonempty, bool allow_none, int *cnt,
+                      int *status, hipStream_t s) {
+    if (n > 0)
+        hipLaunchKernelGGL(k_grp_count, dim3(grp_grid(n)), dim3(256), 0, s, assign, n, L, nonempty, allow_none ? 1 : 0,
+                           cnt, status);
+}
+
+void launch_grp_scan(const int *cnt, int64_t L, int pad, int64_t *off, int64_t *info, const int *status,
+                     hipStream_t s) {
+    hipLaunchKernelGGL(k_grp_scan, dim3(1), dim3(1024), 0, s, cnt, L, pad, off, info, status);
+}
+
+void launch_grp_scatter(const int32_t *assign, int64_t n, int64_t L, const uint8_t *nonempty, const int64_t *off,
+                        int *fill, int32_t *perm, hipStream_t s) {
+    if (n > 0)
+        hipLaunchKernelGGL(k_grp_scatter, dim3(grp_grid(n)), dim3(256), 0, s, assign, n, L, nonempty, off, fill, perm);
+}
+
+int32_t *launch_grp_sort(int32_t *perm, int32_t *tmp, const int64_t *off, const int *cnt, int64_t L, int64_t npos,
+                         int64_t max_rows, hipStream_t s) {
+    if (npos <= 0 || max_rows < 2) return perm;
+    const int64_t runs = (max_rows + kSortCap - 1) / kSortCap;
+    hipLaunchKernelGGL(k_grp_sort, dim3((unsigned)std::min<int64_t>(L, 2048), (unsigned)std::min<int64_t>(runs, 128)),
+                       dim3(256), 0, s, perm, off, cnt, L);
+    int32_t *src = perm, *dst = tmp;
+    for (int64_t w = kSortCap; w < max_rows; w *= 2) {
+        hipLaunchKernelGGL(k_grp_merge, dim3(grp_grid(npos)), dim3(256), 0, s, src, dst, off, cnt, L, npos, w);
+        std::swap(src, dst);
+    }
+    return src;
+}
+
+void launch_grp_assign_of(const int32_t *perm, const int64_t *off, int64_t L, int64_t npos, int64_t n,
+                          int32_t *assign, hipStream_t s) {
+    if (npos > 0)
+        hipLaunchKernelGGL(k_grp_assign_of, dim3(grp_grid(npos)), dim3(256), 0, s, perm, off, L, npos, n, assign);
+}
+
+void launch_grp_canon(const int64_t *assign, int64_t n, int64_t L, const uint8_t *nonempty, int32_t *out,
+                      hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(k_grp_canon, dim3(grp_grid(n)), dim3(256), 0, s, assign, n, L, nonempty, out);
+}
+
 }  // namespace mqvs

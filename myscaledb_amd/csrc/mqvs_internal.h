@@ -535,6 +535,33 @@ void launch_words_to_host(const int64_t *a, int na, const int *b, int nb, int64_
 bool launch_scan_p4_groups(const ScanParams &p, int metric, hipStream_t s);
 void launch_centroid_mean(const float *rows, int d, const int32_t *order, const int64_t *off, int nlist, float *cent,
                           hipStream_t s);
+// Rows grouped by list on the device (kernels_ivf.hip; index.hip's
+// finish_index).  assign[n]: list id of each row, -1 = in no list; a row whose
+// nonempty bit (may be null) is clear is in no list.
+// count: cnt[L] (zeroed) rows per list; *status (zeroed) |= kGrpBadRange for a
+// value outside [-1, L) -- it is not counted --, kGrpNoList for a -1 when
+// !allow_none.  scan: off[L + 1] (lengths rounded up to pad) and info[5] =
+// npos, longest list in positions, rows in lists, rows of the longest list,
+// *status.  scatter (after the host has read info: perm[npos] filled with
+// -1, fill[L] zeroed) + sort: perm as a stable counting sort gives it; tmp
+// (npos words) is needed when max_rows > kSortCap, and the result is in the
+// returned one of perm / tmp.
+constexpr int kGrpStatusBadRange = 1, kGrpStatusNoList = 2;
+void launch_grp_count(const int32_t *assign, int64_t n, int64_t L, const uint8_t *nonempty, bool allow_none, int *cnt,
+                      int *status, hipStream_t s);
+void launch_grp_scan(const int *cnt, int64_t L, int pad, int64_t *off, int64_t *info, const int *status,
+                     hipStream_t s);
+void launch_grp_scatter(const int32_t *assign, int64_t n, int64_t L, const uint8_t *nonempty, const int64_t *off,
+                        int *fill, int32_t *perm, hipStream_t s);
+int32_t *launch_grp_sort(int32_t *perm, int32_t *tmp, const int64_t *off, const int *cnt, int64_t L, int64_t npos,
+                         int64_t max_rows, hipStream_t s);
+// assign[perm[pos]] = list of pos (assign[n] filled with -1 by the caller)
+void launch_grp_assign_of(const int32_t *perm, const int64_t *off, int64_t L, int64_t npos, int64_t n,
+                          int32_t *assign, hipStream_t s);
+// a build's nearest-centroid ids (int64; null = all 0) -> canonical assignment:
+// outside [0, L) -> list 0, empty array -> -1
+void launch_grp_canon(const int64_t *assign, int64_t n, int64_t L, const uint8_t *nonempty, int32_t *out,
+                      hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // Binary index path (kernels_bivf.hip, index.hip)

@@ -122,6 +122,35 @@ class VectorIndex:
                                     _ptr(_host_u8(row_exists)), _ptr(ids), _ptr(dist), fs, None))
         return ids, dist
 
+    def save(self) -> bytes:
+        """The index as one byte string (mqvs_index_save; VIWithColumnInPart::
+        serialize): centroids, each row's list, nlist, alpha, np95.  A row-ids
+        map is not part of it."""
+        size = ctypes.c_size_t()
+        check(lib.mqvs_index_save_size(self._h, ctypes.byref(size)))
+        buf = np.empty(size.value, np.uint8)
+        written = ctypes.c_size_t()
+        check(lib.mqvs_index_save(self._h, _ptr(buf), buf.size, ctypes.byref(written)))
+        return buf[: written.value].tobytes()
+
+    @classmethod
+    def load(cls, segment, blob):
+        """The index of a save()d byte string over the resident segment it was
+        built on, without a build (mqvs_index_load; VIWithColumnInPart::load)."""
+        b = np.frombuffer(bytes(blob), np.uint8)
+        h = ctypes.c_void_p()
+        check(lib.mqvs_index_load(segment._h, _ptr(b), b.size, ctypes.byref(h)))
+        return cls(h, segment)
+
+    def lists(self):
+        """(list_off int64[nlist + 1], rows int32[npos]): the part row of every
+        list position in position order, -1 = padding (mqvs_index_lists)."""
+        info = self.info()
+        off = np.empty(info["nlist"] + 1, np.int64)
+        rows = np.empty(info["npos"], np.int32)
+        check(lib.mqvs_index_lists(self._h, _ptr(off), off.size, _ptr(rows), rows.size))
+        return off, rows
+
     def compute_top_distance_subset(self, queries, first_stage_ids, top_k, row_exists=None):
         """Exact re-rank of stage-1 ids (segment-local rows, -1 = none)."""
         ids = np.asarray(first_stage_ids, np.int64)
@@ -157,6 +186,9 @@ class BinaryVectorIndex:
 
     set_row_ids_map = VectorIndex.set_row_ids_map
     info = VectorIndex.info
+    save = VectorIndex.save
+    load = classmethod(VectorIndex.load.__func__)
+    lists = VectorIndex.lists
 
     def _host_queries(self, queries):
         q = _host_u8(queries)
@@ -225,6 +257,15 @@ class BinaryVectorIndex:
 
 def last_index_stats():
     return _lib.last_index_stats()
+
+
+def index_blob_info(blob):
+    """The header fields of a saved index (mqvs_index_blob_info: host only; the
+    first block must be stored uncompressed, as save() writes it)."""
+    b = np.frombuffer(bytes(blob), np.uint8)
+    st = _lib.IndexBlobInfo()
+    check(lib.mqvs_index_blob_info(_ptr(b), b.size, ctypes.byref(st)))
+    return {f: getattr(st, f) for f, _ in _lib.IndexBlobInfo._fields_}
 
 
 def decoupled_filter(new_filter, new_rows, inverted_row_ids_map, inverted_row_sources_map, own_id, old_rows):
