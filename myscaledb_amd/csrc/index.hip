@@ -113,19 +113,17 @@ struct IndexWorkspace final : WsExt {
     hipEvent_t fork = nullptr, join = nullptr;
     hipStream_t side = nullptr;
     int64_t *host = nullptr;  // pinned: the search's stats [4] and status word (one sync, no staging copies)
-    HostBuf pin_q, pin_f, pin_e, pin_o;  // pinned staging of host-pointer searches
-    GBuf queries, qvars, qnorms, qmu, qlam, status, qhi, probes, cprobes, filter, exists, rows, out_ids, out_dist,
-        ord, dmap, dwords, pdist, cqhi, gmax, crec, cbq, craw, ibq, qdelta, pstats;
+    CallIO io;  // staged inputs and outputs of host-pointer searches
+    GBuf qvars, qnorms, qmu, qlam, status, qhi, probes, cprobes, rows, ord, dmap, dwords, pdist, cqhi, gmax, crec, cbq,
+        craw, ibq, qdelta, pstats;
     ListBufs coarse, fine;
     // WsExt: the owner is between calls (its workspace's `done` event passed:
     // the main stream, which joins the side chain, has drained)
     size_t free_scratch() override {
         if (side) (void)hipStreamSynchronize(side);
-        size_t b = 0;
-        for (HostBuf *x : {&pin_q, &pin_f, &pin_e, &pin_o}) x->release();  // (host memory: not counted)
-        for (GBuf *x : {&queries, &qvars, &qnorms, &qmu, &qlam, &status, &qhi, &probes, &cprobes, &filter, &exists,
-                        &rows, &out_ids, &out_dist, &ord, &dmap, &dwords, &pdist, &cqhi, &gmax, &crec, &cbq, &craw,
-                        &ibq, &qdelta, &pstats}) {
+        size_t b = io.release();
+        for (GBuf *x : {&qvars, &qnorms, &qmu, &qlam, &status, &qhi, &probes, &cprobes, &rows, &ord, &dmap, &dwords,
+                        &pdist, &cqhi, &gmax, &crec, &cbq, &craw, &ibq, &qdelta, &pstats}) {
             b += x->cap;
             x->release();
         }
@@ -181,7 +179,6 @@ static IndexWorkspace &index_workspace(int device) {
     return w;
 }
 
-static int64_t rup(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 // ---- Search::Parameters: "k=v,k=v" ----------------------------------------
 static std::map<std::string, std::string> parse_params(const char *s) {
@@ -272,7 +269,7 @@ static void group_by_list(const std::vector<int64_t> &assign, int64_t L, int64_t
         if (a >= 0 && a < L) ++cnt[a];
     }
     off.assign(L + 1, 0);
-    for (int64_t l = 0; l < L; ++l) off[l + 1] = off[l] + rup(cnt[l], pad);
+    for (int64_t l = 0; l < L; ++l) off[l + 1] = off[l] + round_up(cnt[l], pad);
     order.assign(off[L], -1);
     std::vector<int64_t> cur(off.begin(), off.end() - 1);
     for (size_t i = 0; i < assign.size(); ++i) {
@@ -338,7 +335,7 @@ static void check_index_width(mqvs_segment *seg) {
     const int d = seg->d;
     DeviceGuard guard(seg->device);
     const int64_t lim = device_lds_bytes();
-    if (ivf_fit_qg(16, rup(d, kBfK), lim) == 0) {
+    if (ivf_fit_qg(16, round_up(d, kBfK), lim) == 0) {
         int64_t dmax = (lim / 16 - 32) / 2 / kBfK * kBfK;
         fail(MQVS_ERR_BAD_ARGUMENTS, "dimension " + std::to_string(d) + " is too wide for an index: the list scan's " +
                                          "16-query tile must fit the workgroup's " + std::to_string(lim) +
@@ -410,7 +407,7 @@ static void finish_index(mqvs_index *ix, const int32_t *assign, bool from_blob, 
     // bound pruning off)
     ix->yrec = dalloc<float>(ix, kMxRec);
     MQVS_HIP(hipMemsetAsync(ix->yrec, 0, sizeof(float) * kMxRec, s));
-    launch_to_hi(seg->rows, n, d, d, ix->dpad, 1, rup(n, 16), nullptr, nullptr, ix->yrec, s);
+    launch_to_hi(seg->rows, n, d, d, ix->dpad, 1, round_up(n, 16), nullptr, nullptr, ix->yrec, s);
     MQVS_HIP(hipGetLastError());
     // ---- coarse quantizer as lists of kCoarseChunk centroids
     ix->cnl = (L + kCoarseChunk - 1) / kCoarseChunk;
@@ -497,7 +494,7 @@ static mqvs_index *build_impl(mqvs_segment *seg, const char *index_type, const c
         ix->coarse_metric = metric == MQVS_METRIC_L2 ? MQVS_METRIC_L2 : kMetricIpRaw;
         ix->nlist = std::max<int64_t>(L, 1);
         ix->alpha = (float)num_param(pm, "alpha", 3.0, 1.0, 4.0);
-        ix->dpad = rup(d, kBfK);
+        ix->dpad = round_up(d, kBfK);
         const int cseg_metric = metric == MQVS_METRIC_L2 ? MQVS_METRIC_L2 : MQVS_METRIC_IP;
 
         // rows that can be indexed: non-empty arrays
@@ -885,17 +882,13 @@ static int64_t *list_pass(ListBufs &b, const uint16_t *plane, const int32_t *per
 static thread_local int64_t *t_probes_out = nullptr;
 
 // formula_nq: the call's batch size, which selects the exact re-rank's
-// distance formula (0: nq; query sub-batches keep the call's, see mqvs.hip)
+// distance formula (0: nq; query sub-batches keep the call's, see search.hip)
 static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int k, const char *params,
                               const uint8_t *filter, const uint8_t *exists, int64_t *out_ids, float *out_dist,
                               uint32_t flags, hipStream_t user_stream, int formula_nq, int maxv_hint) {
     const int fnq = formula_nq > 0 ? formula_nq : nq;
-    if (!ix) fail(MQVS_ERR_BAD_ARGUMENTS, "null index");
-    if (ix->binary) fail(MQVS_ERR_LOGICAL, "binary index: search it with mqvs_index_search_binary");
-    if (nq < 0 || k < 0) fail(MQVS_ERR_BAD_ARGUMENTS, "nq and k must be non-negative");
-    if (nq > 0 && k > 0 && (!queries || !out_ids || !out_dist))
-        fail(MQVS_ERR_BAD_ARGUMENTS, "null query or output pointer");
-    if (k > kMaxK) fail(MQVS_ERR_BAD_ARGUMENTS, "k above " + std::to_string(kMaxK) + " not supported");
+    check_search_args(ix, "index", ix && ix->binary ? "binary index: search it with mqvs_index_search_binary" : nullptr,
+                      nq, k, queries, out_ids, out_dist);
     const auto pm = parse_params(params);
     check_keys(pm, {"alpha", "nprobe", "num_reorder"}, "search");
     const bool first_stage = flags & MQVS_F_FIRST_STAGE;
@@ -922,11 +915,10 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
         const int qb = (int)std::max<int64_t>(1, (int64_t)scratch_budget() / 16 / (2 * (int64_t)R));
         if (nq > qb) {
             const int d = ix->seg->d;
-            for (int q0 = 0; q0 < nq; q0 += qb) {
-                const int m = std::min(qb, nq - q0);
+            for_query_batches(nq, qb, [&](int q0, int m) {
                 search_index_impl(ix, queries + (size_t)q0 * d, m, k, params, filter, exists,
                                   out_ids + (size_t)q0 * k, out_dist + (size_t)q0 * k, flags, user_stream, fnq);
-            }
+            });
             g_istats.nq = nq;
             return;
         }
@@ -961,30 +953,13 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
     const bool tev = timing_on(flags);
     if (tev) MQVS_HIP(hipEventRecord(ws.ev[0], s));
 
-    const float *dq = queries;
-    const uint8_t *dfilter = filter, *dexists = exists;
-    const int64_t bm = (seg->n + 7) / 8;
-    if (!dev) {
-        float *q = (float *)ws.queries.get(sizeof(float) * (size_t)nq * d);
-        stage_in(ws.pin_q, q, queries, sizeof(float) * (size_t)nq * d, s);
-        dq = q;
-        if (filter) {
-            auto *f = (uint8_t *)ws.filter.get(bm);
-            stage_in(ws.pin_f, f, filter, bm, s);
-            dfilter = f;
-        }
-        if (exists) {
-            auto *f = (uint8_t *)ws.exists.get(bm);
-            stage_in(ws.pin_e, f, exists, bm, s);
-            dexists = f;
-        }
-    }
-    int64_t *dids = out_ids;
-    float *ddist = out_dist;
-    if (!dev) {
-        dids = (int64_t *)ws.out_ids.get(sizeof(int64_t) * (size_t)nq * k);
-        ddist = (float *)ws.out_dist.get(sizeof(float) * (size_t)nq * k);
-    }
+    const CallIO::In in =
+        ws.io.in(queries, sizeof(float) * (size_t)nq * d, filter, exists, (seg->n + 7) / 8, dev, s);
+    const float *dq = (const float *)in.queries;
+    const uint8_t *dfilter = in.filter, *dexists = in.exists;
+    const CallIO::Out out = ws.io.out((size_t)nq * k, dev, out_ids, out_dist);
+    int64_t *dids = out.ids;
+    float *ddist = out.dist;
 
     // ---- query prep: cosine re-normalisation variants (the re-rank uses the
     // row's chunk variant, as mqvs_search does), |q|^2.  The variant table
@@ -996,7 +971,7 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
     // lambda, or < maxv when the chain did not repeat) is written by the prep.
     const int64_t ords = seg->row_offset / seg->granule + (seg->n + seg->granule - 1) / seg->granule;
     const int maxv = cos ? (maxv_hint > 0 ? maxv_hint : kMaxVariants) : 1;
-    const int64_t qstride = rup(d, 32);
+    const int64_t qstride = round_up(d, 32);
     float *qvars = (float *)ws.qvars.get(sizeof(float) * (size_t)nq * maxv * qstride);
     float *qnorms = (float *)ws.qnorms.get(sizeof(float) * nq);
     int *qmu = (int *)ws.qmu.get(sizeof(int) * nq);
@@ -1065,7 +1040,7 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
     }
     if (!picked && cmode == 2 && nprobe <= kCoarsePickMaxT && ix->cent && ix->cent->rows_hi && ix->cent->rows) {
         mqvs_segment *cs = ix->cent;
-        const int64_t vpad = rup(nq, 16);
+        const int64_t vpad = round_up(nq, 16);
         auto *cq = (uint16_t *)ws.cqhi.get(sizeof(uint16_t) * (size_t)vpad * cs->dpad);
         // (variant 0 of every query: the raw query, or the normalised one for
         // cosine -- centroids of cosine parts are normalised: same ranking as
@@ -1093,7 +1068,7 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
         cp.tiles = (cs->n + 255) / 256;
         cp.tiles_per_chunk = 0;
         // groups of 8 centroids: 32 per 256-row tile
-        const int64_t gld = rup(32 * cp.tiles, 4);
+        const int64_t gld = round_up(32 * cp.tiles, 4);
         cp.p4_gmax = (float *)ws.gmax.get(sizeof(float) * (size_t)nq * gld);
         cp.p4_gld = gld;
         if (launch_scan_p4_groups(cp, ix->coarse_metric, s)) {
@@ -1142,7 +1117,7 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
         if (split) qdelta = (float *)ws.qdelta.get(sizeof(float) * (size_t)nq);
         if (!qrec0) {
             qrec0 = (float *)ws.crec.get(sizeof(float) * kMxRec * (size_t)nq);
-            launch_to_hi(qvars, nq, d, (int64_t)maxv * qstride, ix->dpad, 1, rup(nq, 16), nullptr, qrec0, nullptr, s);
+            launch_to_hi(qvars, nq, d, (int64_t)maxv * qstride, ix->dpad, 1, round_up(nq, 16), nullptr, qrec0, nullptr, s);
         }
         ScanParams bp{};
         bp.nq = nq;
@@ -1229,23 +1204,17 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
     if (!dev) {
         // (host outputs: copied before the final wait)
         if (ix->row_ids_map) launch_map_ids(dids, (int64_t)nq * k, ix->row_ids_map, s);
-        stage_out_begin(ws.pin_o, dids, ddist, (size_t)nq * k, s);
+        ws.io.finish_begin(out, s);
     }
     launch_words_to_host(dstats, 4, status, 8, hs, hst, s, stats_per_query ? dstats : nullptr, nq);
     MQVS_HIP(hipGetLastError());
     host_wait(s);
-    const int hstatus = *hst;
-    if (hstatus && !first_stage && ords > maxv) {
-        const int want = (int)std::min<int64_t>(ords, kMaxVariantsCap);
-        if (maxv < want) {
-            search_index_impl(ix, queries, nq, k, params, filter, exists, out_ids, out_dist, flags, user_stream, fnq,
-                              want);
-            return;
-        }
-        fail(MQVS_ERR_LOGICAL, "cosine query normalisation did not repeat within " + std::to_string(maxv) +
-                                   " steps on a part of more chunks");
+    if (const int want = first_stage ? 0 : check_variant_chain(*hst, ords, maxv)) {
+        search_index_impl(ix, queries, nq, k, params, filter, exists, out_ids, out_dist, flags, user_stream, fnq,
+                          want);
+        return;
     }
-    if (!dev) stage_out_end(ws.pin_o, out_ids, out_dist, (size_t)nq * k);
+    ws.io.finish_end(out);
     st.values = hs[0];
     st.items = hs[1];
     st.plane_bytes = hs[2];
@@ -1380,12 +1349,8 @@ static mqvs_index *build_binary_impl(mqvs_segment *seg, const char *params) {
 static void search_binary_index_impl(mqvs_index *ix, const uint8_t *queries, int nq, int k, const char *params,
                                      const uint8_t *filter, const uint8_t *exists, int64_t *out_ids, float *out_dist,
                                      uint32_t flags, hipStream_t user_stream, int64_t *probes_out) {
-    if (!ix) fail(MQVS_ERR_BAD_ARGUMENTS, "null index");
-    if (!ix->binary) fail(MQVS_ERR_LOGICAL, "Float32 index: search it with mqvs_index_search");
-    if (nq < 0 || k < 0) fail(MQVS_ERR_BAD_ARGUMENTS, "nq and k must be non-negative");
-    if (nq > 0 && k > 0 && (!queries || !out_ids || !out_dist))
-        fail(MQVS_ERR_BAD_ARGUMENTS, "null query or output pointer");
-    if (k > kMaxK) fail(MQVS_ERR_BAD_ARGUMENTS, "k above " + std::to_string(kMaxK) + " not supported");
+    check_search_args(ix, "index", ix && !ix->binary ? "Float32 index: search it with mqvs_index_search" : nullptr, nq,
+                      k, queries, out_ids, out_dist);
     const auto pm = parse_params(params);
     check_keys(pm, {"alpha", "nprobe", "num_reorder", "metric"}, "search");
     const int metric = pm.count("metric") ? binary_metric_of(pm.at("metric"), "metric") : ix->metric;
@@ -1414,8 +1379,7 @@ static void search_binary_index_impl(mqvs_index *ix, const uint8_t *queries, int
         const int qb = (int)std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)scratch_budget() / perq));
         if (nq > qb) {
             mqvs_index_search_stats sum{};
-            for (int q0 = 0; q0 < nq; q0 += qb) {
-                const int m = std::min(qb, nq - q0);
+            for_query_batches(nq, qb, [&](int q0, int m) {
                 search_binary_index_impl(ix, queries + (size_t)q0 * seg->code_bytes, m, k, params, filter, exists,
                                          out_ids + (size_t)q0 * k, out_dist + (size_t)q0 * k, flags, user_stream,
                                          probes_out ? probes_out + (size_t)q0 * nprobe : nullptr);
@@ -1427,7 +1391,7 @@ static void search_binary_index_impl(mqvs_index *ix, const uint8_t *queries, int
                 sum.items += g_istats.items;
                 sum.plane_bytes += g_istats.plane_bytes;
                 sum.pairs += g_istats.pairs;
-            }
+            });
             sum.nq = nq;
             sum.k = k;
             sum.nprobe = nprobe;
@@ -1447,28 +1411,13 @@ static void search_binary_index_impl(mqvs_index *ix, const uint8_t *queries, int
     if (tev) MQVS_HIP(hipEventRecord(ws.ev[0], s));
 
     // queries -> zero-padded [nq][code_words]
-    auto *qc = (uint32_t *)ws.queries.get(sizeof(uint32_t) * (size_t)nq * cw);
-    MQVS_HIP(hipMemsetAsync(qc, 0, sizeof(uint32_t) * (size_t)nq * cw, s));
-    MQVS_HIP(hipMemcpy2DAsync(qc, (size_t)cw * 4, queries, (size_t)seg->code_bytes, (size_t)seg->code_bytes, (size_t)nq,
-                              dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    const uint8_t *dfilter = filter, *dexists = exists;
-    const int64_t bm = (seg->n + 7) / 8;
-    int64_t *dids = out_ids;
-    float *ddist = out_dist;
-    if (!dev) {
-        if (filter) {
-            auto *f = (uint8_t *)ws.filter.get(bm);
-            stage_in(ws.pin_f, f, filter, bm, s);
-            dfilter = f;
-        }
-        if (exists) {
-            auto *f = (uint8_t *)ws.exists.get(bm);
-            stage_in(ws.pin_e, f, exists, bm, s);
-            dexists = f;
-        }
-        dids = (int64_t *)ws.out_ids.get(sizeof(int64_t) * (size_t)nq * k);
-        ddist = (float *)ws.out_dist.get(sizeof(float) * (size_t)nq * k);
-    }
+    auto *qc = (uint32_t *)ws.io.queries.get(sizeof(uint32_t) * (size_t)nq * cw);
+    upload_codes(qc, cw, queries, seg->code_bytes, nq, dev, s);
+    const CallIO::In in = ws.io.in(nullptr, 0, filter, exists, (seg->n + 7) / 8, dev, s);
+    const uint8_t *dfilter = in.filter, *dexists = in.exists;
+    const CallIO::Out out = ws.io.out((size_t)nq * k, dev, out_ids, out_dist);
+    int64_t *dids = out.ids;
+    float *ddist = out.dist;
     // [0] the final select's overflow word (never set: a region holds every
     // position of its lists)
     int *status = (int *)ws.status.get(sizeof(int) * 8);
@@ -1534,12 +1483,12 @@ static void search_binary_index_impl(mqvs_index *ix, const uint8_t *queries, int
     }
     int64_t *hs = ws.host;
     int *hst = reinterpret_cast<int *>(ws.host + 4);
-    if (!dev) stage_out_begin(ws.pin_o, dids, ddist, (size_t)nq * k, s);
+    ws.io.finish_begin(out, s);
     launch_words_to_host(dstats, 4, status, 8, hs, hst, s);
     MQVS_HIP(hipGetLastError());
     host_wait(s);
     if (*hst) fail(MQVS_ERR_DEVICE, "binary index search: a query's record region overflowed");
-    if (!dev) stage_out_end(ws.pin_o, out_ids, out_dist, (size_t)nq * k);
+    ws.io.finish_end(out);
     st.values = hs[0];
     st.items = hs[1];
     st.plane_bytes = hs[2];
@@ -1812,7 +1761,7 @@ static mqvs_index *load_impl(mqvs_segment *seg, const uint8_t *blob, size_t byte
                                       hipMemcpyDeviceToDevice, s));
         } else {
             ix->coarse_metric = ix->metric == MQVS_METRIC_L2 ? MQVS_METRIC_L2 : kMetricIpRaw;
-            ix->dpad = rup(seg->d, kBfK);
+            ix->dpad = round_up(seg->d, kBfK);
             ix->cent = segment_from_device((const float *)(c + sizeof(hd)), L, seg->d,
                                            ix->metric == MQVS_METRIC_L2 ? MQVS_METRIC_L2 : MQVS_METRIC_IP, s);
         }

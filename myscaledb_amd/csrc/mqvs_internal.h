@@ -614,8 +614,14 @@ struct Error {
     } while (0)
 
 // ---------------------------------------------------------------------------
-// Host-side plumbing shared by mqvs.hip (segments, FLAT search) and
-// index.hip (the index path)
+// Host-side plumbing shared by the host files: mqvs.hip (the workspace gate,
+// host waits, segments, C ABI glue), search.hip and search_binary.hip
+// (the FLAT searches), index.hip (the index path)
+
+[[noreturn]] inline void fail(int code, const std::string &msg) { throw Error{code, msg}; }
+
+inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+size_t scratch_budget();  // bytes per scratch buffer of one call (mqvs_set_scratch_budget)
 
 struct DevBuf {
     void *p = nullptr;
@@ -664,13 +670,6 @@ struct HostBuf {
         cap = 0;
     }
 };
-// host -> device through `pin` (the CPU copy now, the DMA queued on s)
-inline void stage_in(HostBuf &pin, void *dst, const void *src, size_t bytes, hipStream_t s) {
-    if (!bytes) return;
-    void *h = pin.get(bytes);
-    std::memcpy(h, src, bytes);
-    MQVS_HIP(hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, s));
-}
 
 // Per-thread scratch of another path (the index's, index.hip) counted in, and
 // trimmed with, the calling thread's FLAT workspace under the process-wide
@@ -686,7 +685,8 @@ struct WsExt {
     ~WsExt() = default;
 };
 // a DevBuf whose growth passes the gate of the calling thread's current
-// WsScope (fails outside one: no ungated scratch)
+// workspace call (WsCall, workspace.h; WsScope below is one) -- it fails
+// outside one: no ungated scratch
 struct GBuf : DevBuf {
     void *get(size_t bytes);
 };
@@ -701,8 +701,7 @@ class WsScope {
     WsScope &operator=(const WsScope &) = delete;
 
    private:
-    void *impl_ = nullptr;
-    void *prev_ = nullptr;
+    void *call_ = nullptr;  // the WsCall
 };
 // index_thread_release: `ext`'s scratch freed and detached from the thread's workspace
 void ws_detach_ext(int device, WsExt *ext);
@@ -739,9 +738,7 @@ static int guarded(F &&f) {
     }
 }
 
-[[noreturn]] inline void fail(int code, const std::string &msg) { throw Error{code, msg}; }
-
-// mqvs.hip services used by the index path
+// the stream of the calling thread's workspace on `device`
 hipStream_t thread_stream(int device);
 // compute units of the current device (cached per device: launchers size
 // their persistent grids from it on every call)
@@ -773,16 +770,147 @@ inline uint64_t wait_str_hash(const char *p) {  // (a parameter string's part of
     for (; p && *p; ++p) h = (h ^ (unsigned char)*p) * 1099511628211ull;
     return h;
 }
-// the ids and distances of a synchronous host-pointer call: device ->
-// pinned `pin` -> the caller's arrays (m results each), after the work queued
-// on s (one host_wait)
-void stage_out_results(HostBuf &pin, int64_t *ids, float *dist, const int64_t *dids, const float *ddist, size_t m,
-                       hipStream_t s);
-// the same in two halves, so the call's last host_wait covers the copies:
-// begin queues the device -> pinned copies on s, end (after that wait)
-// copies pinned -> the caller's arrays
-void stage_out_begin(HostBuf &pin, const int64_t *dids, const float *ddist, size_t m, hipStream_t s);
-void stage_out_end(const HostBuf &pin, int64_t *ids, float *dist, size_t m);
+// The inputs and outputs of one search call on the device.  A call with
+// MQVS_F_DEVICE_PTRS (`dev`) uses the caller's pointers as they are; a
+// host-pointer call is staged through the pinned buffers (HostBuf above) into
+// gated device buffers, and its results come back the same way.  Workspace
+// and IndexWorkspace hold one each: an index search's nested FLAT searches
+// must not reuse the outer call's buffers.
+struct CallIO {
+    GBuf queries, filter, exists, out_ids, out_dist;
+    struct In {
+        const void *queries;
+        const uint8_t *filter, *exists;
+    };
+    // queries (`bytes`; none staged when null) and the two row bitmaps
+    // (bm_bytes each, either may be null): the CPU copies now, the DMAs on s
+    In in(const void *q, size_t bytes, const uint8_t *flt, const uint8_t *ex, size_t bm_bytes, bool dev,
+          hipStream_t s) {
+        if (dev) return In{q, flt, ex};
+        In r{nullptr, nullptr, nullptr};
+        if (q) r.queries = put(queries, pin_q, q, bytes, s);
+        if (flt) r.filter = (const uint8_t *)put(filter, pin_f, flt, bm_bytes, s);
+        if (ex) r.exists = (const uint8_t *)put(exists, pin_e, ex, bm_bytes, s);
+        return r;
+    }
+    // a host array other than a bitmap (mqvs_rerank's candidate rows) through
+    // the filter bitmap's slot
+    const void *in_list(const void *src, size_t bytes, hipStream_t s) { return put(filter, pin_f, src, bytes, s); }
+    // m ids and distances: where the kernels write them, and where they go
+    struct Out {
+        int64_t *ids;
+        float *dist;
+        int64_t *host_ids;  // null: the caller's device arrays, nothing to copy back
+        float *host_dist;
+        size_t m;
+    };
+    Out out(size_t m, bool dev, int64_t *ids, float *dist) {
+        if (dev) return Out{ids, dist, nullptr, nullptr, m};
+        return Out{(int64_t *)out_ids.get(sizeof(int64_t) * m), (float *)out_dist.get(sizeof(float) * m), ids, dist,
+                   m};
+    }
+    // the results of a host-pointer call in two halves, so the call's last
+    // host_wait covers the copies: begin queues device -> pinned on s, end
+    // (after that wait) copies pinned -> the caller's arrays
+    void finish_begin(const Out &o, hipStream_t s) {
+        if (!o.host_ids) return;
+        auto *h = (unsigned char *)pin_o.get(12 * o.m);
+        if (!o.m) return;
+        MQVS_HIP(hipMemcpyAsync(h, o.ids, 8 * o.m, hipMemcpyDeviceToHost, s));
+        MQVS_HIP(hipMemcpyAsync(h + 8 * o.m, o.dist, 4 * o.m, hipMemcpyDeviceToHost, s));
+    }
+    void finish_end(const Out &o) {
+        if (!o.host_ids || !o.m) return;
+        const auto *h = (const unsigned char *)pin_o.p;
+        std::memcpy(o.host_ids, h, 8 * o.m);
+        std::memcpy(o.host_dist, h + 8 * o.m, 4 * o.m);
+    }
+    // both halves around a host_wait of their own
+    void finish(const Out &o, hipStream_t s) {
+        if (!o.host_ids) return;
+        finish_begin(o, s);
+        host_wait(s);
+        finish_end(o);
+    }
+    // the device buffers' bytes, freed (the pinned ones too: host memory, not counted)
+    size_t release() {
+        size_t b = 0;
+        for (GBuf *x : {&queries, &filter, &exists, &out_ids, &out_dist}) {
+            b += x->cap;
+            x->release();
+        }
+        for (HostBuf *x : {&pin_q, &pin_f, &pin_e, &pin_o}) x->release();
+        return b;
+    }
+
+   private:
+    HostBuf pin_q, pin_f, pin_e, pin_o;
+    // host -> device through `pin`
+    static void *put(GBuf &dst, HostBuf &pin, const void *src, size_t bytes, hipStream_t s) {
+        void *d = dst.get(bytes);
+        if (bytes) {
+            void *h = pin.get(bytes);
+            std::memcpy(h, src, bytes);
+            MQVS_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
+        }
+        return d;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// What every search entry point does the same way (search.hip,
+// search_binary.hip, index.hip)
+
+// `what`: "segment" or "index"; wrong_kind: null, or what to say when the
+// handle is of the other kind (float / binary) than the entry point serves
+inline void check_search_args(const void *handle, const char *what, const char *wrong_kind, int nq, int k,
+                              const void *queries, const void *out_ids, const void *out_dist) {
+    if (!handle) fail(MQVS_ERR_BAD_ARGUMENTS, std::string("null ") + what);
+    if (wrong_kind) fail(MQVS_ERR_LOGICAL, wrong_kind);
+    if (nq < 0 || k < 0) fail(MQVS_ERR_BAD_ARGUMENTS, "nq and k must be non-negative");
+    if (nq > 0 && k > 0 && (!queries || !out_ids || !out_dist))
+        fail(MQVS_ERR_BAD_ARGUMENTS, "null query or output pointer");
+    if (k > kMaxK) fail(MQVS_ERR_BAD_ARGUMENTS, "k above " + std::to_string(kMaxK) + " not supported");
+}
+
+// fn(q0, m) for the query sub-batches [q0, q0 + m) of at most qb queries
+// (queries are independent searches: the entry points re-invoke themselves)
+template <typename F>
+inline void for_query_batches(int nq, int64_t qb, F &&fn) {
+    for (int64_t q0 = 0; q0 < nq; q0 += qb) fn((int)q0, (int)std::min<int64_t>(qb, nq - q0));
+}
+
+// A cosine query whose re-normalisation does not repeat within maxv steps
+// (`status` set by the query prep) is exact only on the part's first maxv
+// chunk ordinals.  Returns the larger table size to re-run the search with,
+// 0 when nothing is wrong (maxv covers every ordinal unless the part has more
+// than kMaxVariantsCap chunks); fails when the largest table did not do, or
+// when the caller cannot re-run (can_retry false).
+inline int check_variant_chain(int status, int64_t ords, int maxv, bool can_retry = true) {
+    if (!status || ords <= maxv) return 0;
+    const int want = (int)std::min<int64_t>(ords, kMaxVariantsCap);
+    if (can_retry && maxv < want) return want;
+    fail(MQVS_ERR_LOGICAL, "cosine query normalisation did not repeat within " + std::to_string(maxv) +
+                               " steps on a part of more chunks");
+}
+
+// Large k (above the LDS sort): the global-scratch sort of the final select,
+// and query sub-batches small enough that the candidate lists and the dense
+// probe matrix stay within a fixed HBM budget.
+inline int large_k_cap(int k) { return (int)std::min<int64_t>(kCandMax, (int64_t)16 * k); }
+inline int large_k_batch(int64_t n, int k) {
+    const int64_t cap = large_k_cap(k);
+    const int64_t probe = std::min<int64_t>(n, (int64_t)((double)k * (double)n / (double)(cap / 3)) + 1);
+    const int64_t budget = (int64_t)scratch_budget();
+    const int64_t by_cand = budget / 8 / cap;                          // 8-B candidates
+    const int64_t by_probe = budget / 4 / std::max<int64_t>(probe, 1);  // fp32 probe values
+    return (int)std::max<int64_t>(1, std::min(by_cand, by_probe));
+}
+// candidate capacity per query (a fixed budget spread over the batch)
+inline int cand_capacity(int nq, int k) {
+    const int cap = (int)std::min<int64_t>(kCandMax, kCandBudget / std::max(nq, 1));
+    return std::max(cap, k > kSortCap ? large_k_cap(k) : kSortCap) / 256 * 256;
+}
 // poll budget of the hybrid wait (microseconds; 0 in MQVS_WAIT_BLOCK, -1 in
 // MQVS_WAIT_RUNTIME): also bounds the spin on a pinned-memory word
 int wait_spin_us();
@@ -790,12 +918,27 @@ int wait_spin_us();
 // hyper-thread and saves power while polling)
 void cpu_relax();
 double measure_read_sweep(size_t bytes, int reps, hipStream_t s, double *best_ms);
-size_t scratch_budget();  // bytes per scratch buffer of one call (mqvs_set_scratch_budget)
+// Thread-local state of mqvs.hip: the stats of the thread's last search
+// (mqvs_last_search_stats), and the per-call mode flags resolved against the
+// process-wide defaults (mqvs_set_*)
+mqvs_search_stats &search_stats();
+int call_batch_mode(uint32_t flags);   // 0: bf16 pre-filter + exact re-rank when possible, 1: fp32 MFMA
+int call_gather_mode(uint32_t flags);  // selective PREWHERE: 0 never gather, 1 when <= 60% selected, 2 always
+// the mid-call drill point of mqvs_inject_fault (MQVS_FAULT_MID_CALL): a
+// filtered mqvs_search right after its selected-row count is queued
+void fault_point_mid();
 // FLAT search of a segment (MergeTreeVSManager::vectorScanWithoutIndex);
 // metric may be kMetricIpRaw (faiss knn_inner_product contract)
 void search_internal(mqvs_segment *seg, const float *queries, int nq, int k, int metric,
                      const uint8_t *filter, const uint8_t *exists, int64_t *out_ids, float *out_dist,
-                     uint32_t flags, hipStream_t stream);
+                     uint32_t flags, hipStream_t stream, int64_t ord_base = -1);
+// the other searches behind the C ABI (search.hip, search_binary.hip)
+void rerank_flat(mqvs_segment *seg, const float *queries, int nq, const int64_t *cand, int ncand, int k, int metric,
+                 const uint8_t *exists, int64_t *out_ids, float *out_dist, uint32_t flags, hipStream_t stream);
+void search_binary(mqvs_segment *seg, const uint8_t *queries, int nq, int k, int metric, const uint8_t *filter,
+                   const uint8_t *exists, int64_t *out_ids, float *out_dist, uint32_t flags, hipStream_t stream);
+// rows of `nbytes` (host or device) -> zero-padded [n][words] on the device
+void upload_codes(uint32_t *dst, int words, const uint8_t *src, int64_t nbytes, int64_t n, bool dev, hipStream_t s);
 // segment from rows already on the current device (copied); granule = n
 mqvs_segment *segment_from_device(const float *dev_rows, int64_t n, int d, int metric, hipStream_t st);
 void segment_release(mqvs_segment *s);

@@ -411,11 +411,8 @@ struct CallArgs {
 void stage_inputs(mqvs_comm *c, const CallArgs &a, const float *&dq, const uint8_t *&dfilter,
                   const uint8_t *&dexists) {
     mqvs_segment *shard = a.shard;
-    if (shard->binary) fail(MQVS_ERR_LOGICAL, "binary segments are not sharded");
-    if (a.nq < 0 || a.k < 0) fail(MQVS_ERR_BAD_ARGUMENTS, "nq and k must be non-negative");
-    if (a.k > kMaxK) fail(MQVS_ERR_BAD_ARGUMENTS, "k above " + std::to_string(kMaxK) + " not supported");
-    if (a.nk && (!a.queries || !a.out_ids || !a.out_dist))
-        fail(MQVS_ERR_BAD_ARGUMENTS, "null query or output pointer");
+    check_search_args(shard, "segment", shard->binary ? "binary segments are not sharded" : nullptr, a.nq, a.k,
+                      a.queries, a.out_ids, a.out_dist);
     dq = a.queries;
     dfilter = a.filter;
     dexists = a.exists;

@@ -17,9 +17,9 @@
 // The switches (this table is the whole list):
 //
 //   name                 default       what it forces                         read in
-//   MQVS_SEG             per nq        "first,growth,target" of the search's  mqvs.hip seg_tune
+//   MQVS_SEG             per nq        "first,growth,target" of the search's  search.hip seg_tune
 //                                      row segments
-//   MQVS_P4_ORD          1             0: no cosine ordinal planes (each      mqvs.hip search_impl
+//   MQVS_P4_ORD          1             0: no cosine ordinal planes (each      search.hip FlatSearch
 //                                      lane picks its query's variant)
 //   MQVS_P4_MAP          1             0: tile sequence x + 8 tg (a kernel    kernels_p4.hip launch_p4_any
 //                                      argument of k_scan_p4m)
@@ -28,7 +28,7 @@
 //   MQVS_HI_REG          1             0: small batches take k_scan_hi, not   kernels_hi.hip launch_hi_t,
 //                                      k_scan_hi_reg                          scan_hi_small_tiles_ok
 //   MQVS_HI_SMALL_TILES  1             0: no kBfRowsSmall-row tiles           kernels_hi.hip scan_hi_small_tiles_ok
-//   MQVS_HI_SMALL_MAIN   1             0: small tiles for probe scans only    mqvs.hip search_impl
+//   MQVS_HI_SMALL_MAIN   1             0: small tiles for probe scans only    search.hip FlatSearch
 //   MQVS_IVF_QG          by pairs per  queries per list-scan group: 16, 32,   index.hip list_pass
 //                        list          64
 //   MQVS_IVF_CHUNK       8 qg          rows per list-scan work item           index.hip list_pass

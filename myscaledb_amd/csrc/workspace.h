@@ -1,0 +1,117 @@
+// workspace.h -- the per-thread device workspace of the FLAT paths and the
+// process-wide gate on the HBM all workspaces hold (mqvs.hip).
+#pragma once
+
+#include <mutex>
+
+#include "mqvs_internal.h"
+
+namespace mqvs {
+
+// the pinned record [padded, selected, generation] of k_chunk_count (int64
+// words at host_flags + kCountRec), and how long a filtered search polls it
+constexpr int kCountRec = 32;
+constexpr int kCountSpinUs = 200;
+
+// One thread's scratch on one device.  Every buffer is a GBuf: it grows
+// through the gate (Workspace::grow) of the thread's current WsCall.
+struct Workspace {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[6] = {};
+    static constexpr int kSegEv = 64;
+    hipEvent_t seg_ev[kSegEv] = {};  // per main-scan segment: start, end
+    CallIO io;                       // staged inputs and outputs of host-pointer calls
+    GBuf qvars, qnorms, qmu, qlam, status, ord, probe, tau, count, cand, overflow, misc, qhi, bq, thr, cand2, count2,
+        gcount, goff, glist, large, sticky, surv, recs, flags, p4q, qord;
+    int *host_flags = nullptr;  // pinned (64 ints; the selected-row count record at kCountRec)
+    int64_t count_gen = 0;      // generation of the last selected-row count record asked for
+    bool pending_timing = false, pending_bf16 = false;  // search_collect_stats
+    int pending_seg_events = 0;
+    int device = 0;
+    std::mutex use;     // held by the owning thread during a call (WsCall); trimmers only try_lock it
+    hipStream_t last = nullptr;  // the stream of the current call (the caller's, or `stream`)
+    hipEvent_t done = nullptr;   // recorded on it at the end of every call: a trimmer waits for it
+    int depth = 0;      // the owner's nested calls
+    size_t held = 0;    // device bytes of the buffers (the gate's share of this workspace)
+    size_t resv = 0;    // the current call's reservation left
+    size_t call_peak = 0, recent = 0;  // most held during the current / the last call
+    WsExt *ext = nullptr;  // the thread's index workspace: its scratch is counted and trimmed with this one
+    bool trimming = false;  // picked by a trimmer, which waits and frees outside the gate mutex
+    void init(int dev);
+    // the buffers, sticky word included (gate accounting is the caller's)
+    size_t free_buffers(bool keep_sticky);
+    size_t trim();
+    void release();
+    // b grown to `bytes` through the gate (GBuf::get; the ASYNC sticky word
+    // grows outside a call too)
+    void *grow(DevBuf &b, size_t bytes);
+};
+
+// the calling thread's workspace on `device` (created on first use)
+Workspace &workspace(int device);
+
+// one call of the owning thread on its workspace (nests): counted as running
+// and made the thread's current one for GBuf growth; at the end, if other
+// calls wait for memory (or the gate is over budget), the workspace is freed
+// for them
+struct WsCall {
+    Workspace &ws;
+    explicit WsCall(Workspace &w);
+    ~WsCall();
+    WsCall(const WsCall &) = delete;
+    WsCall &operator=(const WsCall &) = delete;
+
+   private:
+    Workspace *prev_;
+};
+
+// ASYNC searches cannot run the host-driven fallbacks (exact re-scan after a
+// pre-filter overflow, tightened re-scan, the cosine variant check): their
+// device flags are OR-ed into this thread's sticky word, which
+// mqvs_async_check reads and clears.
+int *sticky_word(Workspace &ws, hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// shared by search.hip and search_binary.hip
+
+// per-stage times of the search just synchronised (HIP events on its stream);
+// seg_events: the main-scan segments whose start / end events were recorded
+// (0: main_ms is the whole span between the probe select and the final select)
+void read_search_times(Workspace &ws, mqvs_search_stats &st, int seg_events);
+
+// The host-driven answer to a candidate-list overflow (more than cap rows at
+// or under the probe threshold; rare): while the overflow word read into
+// ws.host_flags[0] is set, tighten tau from what was kept, re-scan the part
+// inclusively (`rescan`) and select again -- at most 3 times.  Returns the
+// number of re-scans.
+struct OverflowRescan {
+    Cand *cand;
+    int *count;
+    int cap, nq, k, order;  // order: the metric whose key orders the candidates
+    uint32_t *tau;
+    int *overflow;
+    int64_t chunk_rows, id_offset;  // of the final select
+    int64_t *dids;
+    float *ddist;
+    uint4 *large;
+};
+template <typename Scan>
+int rescan_on_overflow(Workspace &ws, const OverflowRescan &r, hipStream_t s, Scan &&rescan) {
+    int rescans = 0;
+    while (ws.host_flags[0]) {
+        if (++rescans > 3)
+            fail(MQVS_ERR_LOGICAL, "candidate overflow: more than " + std::to_string(r.cap) +
+                                       " rows tie at the k-th distance");
+        launch_cand_tau(r.cand, r.count, r.cap, r.nq, r.k, r.order, r.tau, nullptr, s);
+        launch_fill2((uint32_t *)r.count, r.nq, 0u, (uint32_t *)r.overflow, 4, 0u, s);
+        rescan();
+        launch_final_select(r.cand, r.count, r.cap, r.nq, r.k, r.order, r.chunk_rows, r.id_offset, r.dids, r.ddist,
+                            r.overflow, r.large, s);
+        MQVS_HIP(hipGetLastError());
+        MQVS_HIP(hipMemcpyAsync(ws.host_flags, r.overflow, sizeof(int), hipMemcpyDeviceToHost, s));
+        host_wait(s);
+    }
+    return rescans;
+}
+
+}  // namespace mqvs

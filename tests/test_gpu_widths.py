@@ -5,8 +5,8 @@ Two seeded generator parts (as run_parity builds them) carry every case:
 
 * the main-scan part, n = 36901: above the 32768 rows at which
   search_internal switches from a dense probe of every row to a probe plus a
-  segmented main scan (mqvs.hip:1275, `scan_n > 32768`), with a partial last
-  tile and granule (granule 2048 for cosine: 19 chunk ordinals, so several
+  segmented main scan (`FlatSearch::plan_probe` in search.hip,
+  `scan_n > 32768`), with a partial last tile and granule (granule 2048 for cosine: 19 chunk ordinals, so several
   query variants are in play).  `main_rows > 0` proves the main scan ran;
 * the probe-only part, its first 3001 rows: P = scan_n, so the PROBE
   instantiations alone decide the candidates (`main_rows == 0`).
@@ -22,9 +22,9 @@ launch_hi_t (kernels_hi.hip:563-594), for the probe and the main scan:
   3. else nq <= 64: k_scan_hi<1,2,3>; nq <= 128: k_scan_hi<2,2,3>; more (the
      PROBE scan of a large batch): k_scan_hi<2,4,4> -- runtime loops over
      dpad / 32 stages through a ring of LDS buffers.
-  The probe of nq <= 2 queries takes 64-row tiles (mqvs.hip:1298-1300 with
-  scan_hi_small_tiles_ok, kernels_hi.hip:515-520: the TILE form of the
-  register kernel).
+  The probe of nq <= 2 queries takes 64-row tiles (`ptile` in
+  `FlatSearch::plan_probe` with scan_hi_small_tiles_ok,
+  kernels_hi.hip:515-520: the TILE form of the register kernel).
 Exact kernels (launch_small_t / launch_mfma_t under batch mode 1 or without
 planes, launch_exact_rerank on the default path): float4 rows when
 d % 4 == 0, scalar loads otherwise; the one-wave re-rank only when
