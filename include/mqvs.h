@@ -359,7 +359,33 @@ int mqvs_generate_device(uint64_t seed, int32_t mode, int64_t row0, int64_t n, i
  *   nlist        lists (default about n / 256, at most 65536)
  *   kmeans_iters k-means iterations (default 8)
  *   sample       k-means training rows (default min(n, max(16 nlist, min(64 nlist, 2^20))))
+ *   plane        bf16 | fp8 (case-insensitive; default bf16): the number format
+ *                of the list plane, below; any other value fails with
+ *                MQVS_ERR_BAD_ARGUMENTS
  * Unknown keys fail with MQVS_ERR_BAD_ARGUMENTS.
+ * plane=fp8 stores the list plane at 1 byte per element (OCP e4m3fn codes with
+ * one power-of-two scale per list position) instead of 2, so the index takes
+ * about half the HBM and a list scan streams half the bytes.  The quantiser,
+ * per row y at a list position p (and per query, once per search): amax = max
+ * |y_i|; if amax is finite and non-zero, E = the frexp exponent of amax (amax
+ * = m 2^E, m in [0.5, 1)) and e_p = 8 - E, else e_p = 0; the stored code of y_i
+ * is e4m3fn(y_i 2^e_p), rounded to nearest even (scaled magnitudes lie in
+ * [128, 256), under e4m3's 448; a scaled value that is not finite is stored
+ * as the NaN code); padding positions and columns >= dim are zero codes.  The
+ * approximate inner product of a row and a query is acc 2^-(e_p + e_q), scaled
+ * in one exact step, where acc is the fp32 MFMA sum of the code products, each
+ * exact in fp32 (the scan widens the codes to bf16, which holds every e4m3
+ * value, and sums with the bf16 MFMA: the fp8 MFMA of an MI355X keeps about 13
+ * bits under the largest product of an instruction); L2 is
+ * (|q|^2 + |y|^2) - 2 ip with the exact fp32 norms.  Only the candidate set
+ * and the size of the re-rank's pruning bound change: every returned distance
+ * is still the exact fp32 one, and a search that probes every list with
+ * num_reorder candidates enough returns mqvs_search's bits.  The coarse
+ * quantizer (centroids, mqvs_index_probes) stays bf16 / fp32: an fp8 index
+ * probes the lists the bf16 index over the same centroids probes.  A build
+ * that chooses nlist from the data (no nlist, >= 2^20 rows) measures np95 by
+ * searching the index it built, so with plane=fp8 it measures the fp8 plane.
+ * The width limit is shared by both formats (the same bf16 query tile).
  * Width limit: the list scan keeps a tile of 16, 32 or 64 bf16 queries in LDS,
  * 16 QB (2 dpad + 16) + 256 QB bytes for 16 QB queries (dpad: the dimension
  * rounded up to 64), and uses the largest tile that fits the device's
@@ -381,6 +407,15 @@ typedef struct {
     double build_ms;
 } mqvs_index_info_t;
 int mqvs_index_info(mqvs_index_t idx, mqvs_index_info_t *out);
+/* The list plane of a float index: *format = MQVS_INDEX_PLANE_BF16 or
+ * MQVS_INDEX_PLANE_FP8 (build parameter `plane`), *plane_bytes = the HBM bytes
+ * of the list plane (npos x dpad elements of 2 or 1 bytes) plus, for fp8, its
+ * per-position scale exponents (int16: 2 npos bytes); mqvs_index_info's
+ * hbm_bytes counts them.  Either output may be NULL.  A binary index fails
+ * with MQVS_ERR_LOGICAL. */
+#define MQVS_INDEX_PLANE_BF16 0
+#define MQVS_INDEX_PLANE_FP8 1
+int mqvs_index_plane(mqvs_index_t idx, int32_t *format, size_t *plane_bytes);
 /* Search params (comma-separated key=value, may be NULL or ""):
  *   alpha        [1, 4]: probes nprobe(alpha) lists (more = higher recall; alpha 3:
  *                max(4, nlist / 256, lists of 4096 rows), doubling per unit)
@@ -393,7 +428,7 @@ int mqvs_index_info(mqvs_index_t idx, mqvs_index_info_t *out);
  * filter / row_exists: LSB-first bitmaps over the segment's rows, or NULL.
  * Output as mqvs_search (k per query, reference order, -1 padding).  With
  * MQVS_F_FIRST_STAGE the call returns the first stage only: the k best rows
- * by the approximate bf16 distance (approximate distances), to be re-ranked
+ * by the approximate distance of the index's plane format (bf16 or fp8), to be re-ranked
  * by mqvs_rerank (the reference's two-stage search). */
 #define MQVS_F_FIRST_STAGE 0x8u
 /* Re-rank every one of the num_reorder candidates.  By default a candidate
@@ -515,7 +550,10 @@ int mqvs_index_probes_binary(mqvs_index_t idx, const uint8_t *queries, int32_t n
  *   bytes 40-43  alpha, the default search alpha, as fp32 bits
  *   bytes 44-47  UInt32 np95 (0: not measured; see mqvs_index_build)
  *   bytes 48-55  UInt64 fingerprint of the segment's resident rows (below)
- *   bytes 56-63  reserved, zero
+ *   bytes 56-59  UInt32 list plane format (MQVS_INDEX_PLANE_*: 0 bf16, 1 fp8;
+ *                zero on a binary index).  The load rebuilds the plane in this
+ *                format; any other value is a malformed header.
+ *   bytes 60-63  reserved, zero
  *   bytes 64-    the centroid table: nlist x dim fp32 as mqvs_index_centroids
  *                returns it (float), nlist x dim_bits / 8 bytes as
  *                mqvs_index_centroids_binary returns it (binary)
@@ -525,7 +563,7 @@ int mqvs_index_probes_binary(mqvs_index_t idx, const uint8_t *queries, int32_t n
  * Nothing in it depends on the kernels' layouts (list padding, plane tiling).
  * Not saved: the row-ids map of a decoupled part (the reference keeps it in
  * the part's own files: register it again with mqvs_index_set_row_ids_map
- * after the load), the bf16 plane, any derived state.
+ * after the load), the list plane (bf16 or fp8), any derived state.
  *
  * Fingerprint: S = min(n, 1024) rows, row floor(i n / S) for i < S, back to
  * back -- a float row as its dim fp32 values as resident (normalised on a
@@ -608,7 +646,7 @@ typedef struct {
     double total_ms;
     int64_t values;       /* approximate values computed (query x probed position) */
     int64_t items;        /* scan work items (list x 16-query group) */
-    int64_t plane_bytes;  /* bf16 plane bytes streamed by the scan */
+    int64_t plane_bytes;  /* list plane bytes streamed by the scan (2 per element for bf16, 1 for fp8) */
     int64_t pairs;        /* (query, list) pairs */
     int32_t nq, k, nprobe, num_reorder;
     int64_t reranked;     /* candidates re-ranked exactly (sum over queries, <= nq x num_reorder): the bf16

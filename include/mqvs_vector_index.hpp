@@ -420,7 +420,10 @@ class GpuIndex
 public:
     /// createVectorIndex(name, IndexType::MSTG, metric, dim, total_vec, params)
     /// + build (VIWithDataPart.cpp:416-447).  params: "key=value,..." as
-    /// include/mqvs.h documents (metric_type, alpha, nlist, kmeans_iters, sample).
+    /// include/mqvs.h documents (metric_type, alpha, nlist, kmeans_iters, sample,
+    /// plane).  "plane=fp8" keeps the list plane at 1 byte per element (half
+    /// the index's HBM and half the bytes a list scan streams); results stay
+    /// exact, see planeFormat().
     GpuIndex(const PartScan & part_, const std::string & index_type = "MSTG", const std::string & params = "")
         : part(part_)
     {
@@ -434,6 +437,14 @@ public:
 
     mqvs_index_t handle() const { return idx->h; }
     const PartScan & segment() const { return part; }
+    /// MQVS_INDEX_PLANE_BF16 or MQVS_INDEX_PLANE_FP8 (build parameter `plane`);
+    /// plane_bytes (optional): the list plane's HBM bytes (mqvs_index_plane).
+    int32_t planeFormat(size_t * plane_bytes = nullptr) const
+    {
+        int32_t format = 0;
+        check(mqvs_index_plane(idx->h, &format, plane_bytes));
+        return format;
+    }
     mqvs_index_t release() const
     {
         idx->owned = false;

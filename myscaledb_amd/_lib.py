@@ -37,6 +37,7 @@ F_GATHER_NEVER = 0x40
 F_GATHER_ALWAYS = 0x80
 F_TIMING = 0x100
 F_RERANK_ALL = 0x200
+INDEX_PLANE_BF16, INDEX_PLANE_FP8 = 0, 1
 WAIT_RUNTIME, WAIT_HYBRID, WAIT_BLOCK = 0, 1, 2
 
 # Exported C symbols: every one of these is declared in include/mqvs.h.
@@ -49,7 +50,7 @@ SYMBOLS = [
     "mqvs_last_search_stats", "mqvs_set_timing", "mqvs_set_batch_mode", "mqvs_set_gather_mode", "mqvs_set_prefilter",
     "mqvs_set_scratch_budget", "mqvs_measure_read_bandwidth", "mqvs_set_workspace_budget", "mqvs_workspace_stats",
     "mqvs_index_build", "mqvs_index_free", "mqvs_index_info", "mqvs_index_search", "mqvs_index_last_stats",
-    "mqvs_index_centroids", "mqvs_index_probes",
+    "mqvs_index_centroids", "mqvs_index_probes", "mqvs_index_plane",
     "mqvs_index_search_binary", "mqvs_index_centroids_binary", "mqvs_index_probes_binary",
     "mqvs_index_save_size", "mqvs_index_save", "mqvs_index_load", "mqvs_index_blob_info", "mqvs_index_lists",
     "mqvs_segment_create_binary", "mqvs_search_binary", "mqvs_knn_binary_raw",
@@ -173,6 +174,7 @@ def _load(path=LIB_PATH):
         "mqvs_index_last_stats": ([P], ctypes.c_int),
         "mqvs_index_centroids": ([P, P, I64], ctypes.c_int),
         "mqvs_index_probes": ([P, P, I32, ctypes.c_char_p, P], ctypes.c_int),
+        "mqvs_index_plane": ([P, P, P], ctypes.c_int),
         "mqvs_index_search_binary": ([P, P, I32, I32, ctypes.c_char_p, P, P, P, P, U32, P], ctypes.c_int),
         "mqvs_index_centroids_binary": ([P, P, I64], ctypes.c_int),
         "mqvs_index_probes_binary": ([P, P, I32, ctypes.c_char_p, P], ctypes.c_int),

@@ -22,7 +22,8 @@
 //   coarse   FLAT search of the queries against the centroid segment, k =
 //            nprobe (L2 for L2 parts, raw inner product for IP and cosine)
 //   plan     (query, list) pairs grouped by list into 16-query work items
-//   scan     bf16 MFMA over each probed list (kernels_ivf.hip)
+//   scan     bf16 MFMA over each probed list (kernels_ivf.hip); an index built
+//            with plane=fp8 keeps e4m3fn codes there, widened in registers
 //   select   num_reorder best approximate values per query
 //   re-rank  exact fp32 distances of those rows (k_rerank_ids: the formula
 //            and cosine query variant of mqvs_search / mqvs_rerank), top-k by
@@ -52,11 +53,18 @@ struct mqvs_index {
     float alpha = 3.0f;            // default search alpha
     mqvs_segment *cent = nullptr;  // centroid segment (k-means assignment during the build)
     uint16_t *plane = nullptr;     // bf16 rows in list order, [npos/16][dpad/32][16][32] (k_ivf_pack)
+    // plane=fp8 (plane_fmt MQVS_INDEX_PLANE_FP8; `plane` is then null): e4m3fn
+    // codes in list order, [npos/16][dpad/64][16][64], and each position's
+    // scale exponent (k_to_fp8)
+    int plane_fmt = MQVS_INDEX_PLANE_BF16;
+    uint8_t *plane8 = nullptr;
+    int16_t *pscale = nullptr;
     int32_t *perm = nullptr;       // [npos] row of each position, -1 = padding
     float *pnorm = nullptr;        // [npos] |y|^2
     int64_t *list_off = nullptr;   // [nlist+1]
     float *yrec = nullptr;         // [kMxRec] maxima over the rows of |bf16(y)|, |y - bf16(y)|, |y| (the
-                                   // re-rank's bound pruning: k_query_bound's segment record)
+                                   // re-rank's bound pruning: k_query_bound's segment record; fp8: of
+                                   // the de-scaled codes, over the indexed positions)
     // coarse quantizer in the same list layout: the centroids in chunks of
     // kCoarseChunk (every query probes every chunk), bf16 plane + |c|^2
     int64_t cnl = 0, cnpos = 0, cmax = 0;
@@ -115,7 +123,7 @@ struct IndexWorkspace final : WsExt {
     int64_t *host = nullptr;  // pinned: the search's stats [4] and status word (one sync, no staging copies)
     CallIO io;  // staged inputs and outputs of host-pointer searches
     GBuf qvars, qnorms, qmu, qlam, status, qhi, probes, cprobes, rows, ord, dmap, dwords, pdist, cqhi, gmax, crec, cbq,
-        craw, ibq, qdelta, pstats;
+        craw, ibq, qdelta, pstats, q8, q8exp, q8rec;
     ListBufs coarse, fine;
     // WsExt: the owner is between calls (its workspace's `done` event passed:
     // the main stream, which joins the side chain, has drained)
@@ -123,7 +131,7 @@ struct IndexWorkspace final : WsExt {
         if (side) (void)hipStreamSynchronize(side);
         size_t b = io.release();
         for (GBuf *x : {&qvars, &qnorms, &qmu, &qlam, &status, &qhi, &probes, &cprobes, &rows, &ord, &dmap, &dwords,
-                        &pdist, &cqhi, &gmax, &crec, &cbq, &craw, &ibq, &qdelta, &pstats}) {
+                        &pdist, &cqhi, &gmax, &crec, &cbq, &craw, &ibq, &qdelta, &pstats, &q8, &q8exp, &q8rec}) {
             b += x->cap;
             x->release();
         }
@@ -286,7 +294,8 @@ static void free_index(mqvs_index *ix) {
     if (ix->cent) segment_release(ix->cent);
     for (void *q : {(void *)ix->plane, (void *)ix->perm, (void *)ix->pnorm, (void *)ix->list_off, (void *)ix->cplane,
                     (void *)ix->cperm, (void *)ix->cpnorm, (void *)ix->clist_off, (void *)ix->row_ids_map,
-                    (void *)ix->yrec, (void *)ix->bplane, (void *)ix->bcent})
+                    (void *)ix->yrec, (void *)ix->bplane, (void *)ix->bcent, (void *)ix->plane8,
+                    (void *)ix->pscale})
         if (q) (void)hipFree(q);
     if (cur >= 0) (void)hipSetDevice(cur);
     delete ix;
@@ -348,9 +357,10 @@ static void check_index_width(mqvs_segment *seg) {
 // and the canonical assignment -- assign[n] on the device: each row's list, -1
 // for a row in no list -- to the finished index: the rows grouped by list on
 // the device (kernels_ivf.hip: k_grp_*), then everything derived from that:
-// the bf16 plane and |y|^2 in list order, the plane's norm maxima and the
-// coarse quantizer's centroid lists (float), or the codes in list order
-// (binary).  ix: seg, binary, metric, nlist, dpad set.  The assignment is
+// the list plane (bf16, or fp8 codes + scale exponents) and |y|^2 in list
+// order, the plane's norm maxima and the coarse quantizer's centroid lists
+// (float), or the codes in list order (binary).  ix: seg, binary, metric,
+// nlist, dpad, plane_fmt set.  The assignment is
 // range-checked by the kernel that first reads it, and the verdict is read
 // before anything is sized by or indexed with it: from a blob (from_blob) a
 // bad value is the blob's fault, from a build the device's.
@@ -398,17 +408,27 @@ static void finish_index(mqvs_index *ix, const int32_t *assign, bool from_blob, 
         MQVS_HIP(hipGetLastError());
         return;
     }
-    ix->plane = dalloc<uint16_t>(ix, (size_t)ix->npos * ix->dpad);
     ix->pnorm = dalloc<float>(ix, ix->npos);
-    launch_ivf_pack(seg->rows, seg->norms, d, ix->perm, ix->npos, ix->dpad, ix->plane, ix->pnorm, s);
-    MQVS_HIP(hipGetLastError());
-    // the plane's norm maxima (the same bf16 rounding as k_ivf_pack; empty
-    // arrays' FLT_MAX rows make them infinite, which turns the re-rank's
-    // bound pruning off)
     ix->yrec = dalloc<float>(ix, kMxRec);
     MQVS_HIP(hipMemsetAsync(ix->yrec, 0, sizeof(float) * kMxRec, s));
-    launch_to_hi(seg->rows, n, d, d, ix->dpad, 1, round_up(n, 16), nullptr, nullptr, ix->yrec, s);
-    MQVS_HIP(hipGetLastError());
+    if (ix->plane_fmt == MQVS_INDEX_PLANE_FP8) {
+        // codes, scale exponents, |y|^2 and the norm maxima of the indexed
+        // positions in one pass (a non-finite row makes them infinite)
+        ix->plane8 = dalloc<uint8_t>(ix, (size_t)ix->npos * ix->dpad);
+        ix->pscale = dalloc<int16_t>(ix, ix->npos);
+        launch_to_fp8(seg->rows, d, d, ix->perm, ix->npos, ix->dpad, ix->plane8, nullptr, ix->pscale, seg->norms,
+                      ix->pnorm, nullptr, ix->yrec, s);
+        MQVS_HIP(hipGetLastError());
+    } else {
+        ix->plane = dalloc<uint16_t>(ix, (size_t)ix->npos * ix->dpad);
+        launch_ivf_pack(seg->rows, seg->norms, d, ix->perm, ix->npos, ix->dpad, ix->plane, ix->pnorm, s);
+        MQVS_HIP(hipGetLastError());
+        // the plane's norm maxima (the same bf16 rounding as k_ivf_pack; empty
+        // arrays' FLT_MAX rows make them infinite, which turns the re-rank's
+        // bound pruning off)
+        launch_to_hi(seg->rows, n, d, d, ix->dpad, 1, round_up(n, 16), nullptr, nullptr, ix->yrec, s);
+        MQVS_HIP(hipGetLastError());
+    }
     // ---- coarse quantizer as lists of kCoarseChunk centroids
     ix->cnl = (L + kCoarseChunk - 1) / kCoarseChunk;
     std::vector<int64_t> coff(ix->cnl + 1, 0);
@@ -445,7 +465,16 @@ static mqvs_index *build_impl(mqvs_segment *seg, const char *index_type, const c
                                    (seg->binary ? "binary: BINARYMSTG, BINARYIVF" : "Float32: MSTG, IVFFLAT") + ")");
     if (btype) return build_binary_impl(seg, params);
     const auto pm = parse_params(params);
-    check_keys(pm, {"alpha", "metric_type", "nlist", "kmeans_iters", "sample"}, "index");
+    check_keys(pm, {"alpha", "metric_type", "nlist", "kmeans_iters", "sample", "plane"}, "index");
+    int plane_fmt = MQVS_INDEX_PLANE_BF16;
+    if (pm.count("plane")) {
+        std::string pf = pm.at("plane");
+        for (auto &ch : pf) ch = (char)std::tolower((unsigned char)ch);
+        if (pf == "fp8")
+            plane_fmt = MQVS_INDEX_PLANE_FP8;
+        else if (pf != "bf16")
+            fail(MQVS_ERR_BAD_ARGUMENTS, "index parameter `plane` = `" + pm.at("plane") + "` is not one of [bf16,fp8]");
+    }
     int metric = seg->metric;
     if (pm.count("metric_type")) {
         std::string mt = pm.at("metric_type");
@@ -495,6 +524,7 @@ static mqvs_index *build_impl(mqvs_segment *seg, const char *index_type, const c
         ix->nlist = std::max<int64_t>(L, 1);
         ix->alpha = (float)num_param(pm, "alpha", 3.0, 1.0, 4.0);
         ix->dpad = round_up(d, kBfK);
+        ix->plane_fmt = plane_fmt;
         const int cseg_metric = metric == MQVS_METRIC_L2 ? MQVS_METRIC_L2 : MQVS_METRIC_IP;
 
         // rows that can be indexed: non-empty arrays
@@ -604,7 +634,9 @@ static mqvs_index *build_impl(mqvs_segment *seg, const char *index_type, const c
 // sample's own rows are easier queries than held-out ones, and at 0.95 a
 // borderline fine index (mode 2: 0.95 on the sample at nprobe 4, 0.9498 on
 // held-out queries) won by a few per cent and then needed twice the probes in
-// use.  Data of many small clusters (generator mode 3) keeps the fine lists;
+// use.  The evaluation searches the index it built, so with plane=fp8 it
+// measures the fp8 plane (the parameters are passed on to both builds).
+// Data of many small clusters (generator mode 3) keeps the fine lists;
 // data of few large ones (mode 2: 4096 centres over 10M rows) gets the coarse
 // ones.
 struct IndexEval {
@@ -755,13 +787,21 @@ static mqvs_index *build_auto(mqvs_segment *seg, const char *index_type, const c
 // plan, scan and select.  pair_stats ([nq][4] words; null: no pair mode):
 // few pairs per list take pair mode (no plan; the select writes each query's
 // stats there).  Returns the stats words of the pass; *per_query: whether
-// they are pair mode's per-query rows.
+// they are pair mode's per-query rows.  f8 (an fp8 index's fine pass): the
+// plane's codes and scale exponents and the queries' exponents; `plane` is
+// unused and qhi holds the queries' scaled codes as bf16 values.
+struct ListFp8 {
+    const uint8_t *plane8;
+    const int16_t *pscale;
+    const int16_t *qexp;
+};
 static int64_t *list_pass(ListBufs &b, const uint16_t *plane, const int32_t *perm, const float *pnorm,
                           const int64_t *list_off, int64_t nlist, int64_t npos, int64_t max_list, int64_t dpad,
                           int metric, const uint16_t *qhi, const float *qnorm, int nq, const int64_t *probes,
                           int nprobe, const uint8_t *filter, const uint8_t *exists, int R, int64_t *out_rows,
                           int64_t id_offset, float *out_approx, hipEvent_t *ev, hipStream_t s, bool dense = false,
-                          float *out_raw = nullptr, int64_t *pair_stats = nullptr, bool *per_query = nullptr) {
+                          float *out_raw = nullptr, int64_t *pair_stats = nullptr, bool *per_query = nullptr,
+                          const ListFp8 *f8 = nullptr) {
     if (per_query) *per_query = false;
     const int64_t E = (int64_t)nq * nprobe;
     IvfParams p{};
@@ -778,6 +818,13 @@ static int64_t *list_pass(ListBufs &b, const uint16_t *plane, const int32_t *per
     p.qnorm = qnorm;
     p.filter = filter;
     p.exists = exists;
+    p.esize = 2;
+    if (f8) {
+        p.plane8 = f8->plane8;
+        p.pscale = f8->pscale;
+        p.qexp = f8->qexp;
+        p.esize = 1;
+    }
     p.lcount = (int *)b.lcount.get(sizeof(int) * nlist);
     p.lfill = (int *)b.lfill.get(sizeof(int) * nlist);
     p.lstart = (int64_t *)b.lstart.get(sizeof(int64_t) * nlist);
@@ -832,6 +879,7 @@ static int64_t *list_pass(ListBufs &b, const uint16_t *plane, const int32_t *per
         rg.nlist = (int)nlist;
         rg.chunk = p.chunk;
         rg.dpad = dpad;
+        rg.esize = p.esize;
         rg.probes = probes;
         rg.list_off = list_off;
         rg.stats = pair_stats;
@@ -1005,8 +1053,25 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
         MQVS_HIP(hipGetLastError());
         MQVS_HIP(hipEventRecord(ws.join, ws.side));
     };
+    // variant 0 of every query in the list plane's format: bf16, or for an fp8
+    // plane the query's own e4m3fn codes (as the bf16 values the scan's MFMA
+    // takes) with its scale exponent and norm records (the bf16 rounding is
+    // then made only if the coarse step takes the centroid list pass)
+    const bool fp8 = ix->plane_fmt == MQVS_INDEX_PLANE_FP8;
     uint16_t *qhi = (uint16_t *)ws.qhi.get(sizeof(uint16_t) * (size_t)nq * ix->dpad);
-    launch_to_bf16(qvars, nq, d, (int64_t)maxv * qstride, qhi, ix->dpad, s);
+    uint16_t *q8 = nullptr;
+    ListFp8 f8{};
+    float *q8rec = nullptr;
+    if (fp8) {
+        q8 = (uint16_t *)ws.q8.get(sizeof(uint16_t) * (size_t)nq * ix->dpad);
+        auto *q8exp = (int16_t *)ws.q8exp.get(sizeof(int16_t) * (size_t)nq);
+        q8rec = (float *)ws.q8rec.get(sizeof(float) * kMxRec * (size_t)nq);
+        launch_to_fp8(qvars, (int64_t)maxv * qstride, d, nullptr, nq, ix->dpad, nullptr, q8, q8exp, nullptr, nullptr,
+                      q8rec, nullptr, s);
+        f8 = ListFp8{ix->plane8, ix->pscale, q8exp};
+    } else {
+        launch_to_bf16(qvars, nq, d, (int64_t)maxv * qstride, qhi, ix->dpad, s);
+    }
     MQVS_HIP(hipGetLastError());
 
     // ---- coarse: the nprobe nearest centroids, by the same list pass over
@@ -1093,6 +1158,10 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
         search_internal(ix->cent, dq, nq, nprobe, ix->coarse_metric, nullptr, nullptr, probes, pd,
                         MQVS_F_DEVICE_PTRS | (flags & MQVS_F_ASYNC), s);
     } else {
+        if (fp8) {
+            launch_to_bf16(qvars, nq, d, (int64_t)maxv * qstride, qhi, ix->dpad, s);
+            MQVS_HIP(hipGetLastError());
+        }
         list_pass(ws.coarse, ix->cplane, ix->cperm, ix->cpnorm, ix->clist_off, ix->cnl, ix->cnpos, ix->cmax,
                   ix->dpad, ix->metric, qhi, qnorms, nq, cprobes, (int)ix->cnl, nullptr, nullptr, nprobe, probes, 0,
                   nullptr, nullptr, s, true);
@@ -1108,14 +1177,22 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
     }
     // ---- the re-rank's bound pruning (the candidates that cannot reach the
     // exact top k are not re-ranked; same output): per query, the bound on
-    // |bf16 list-scan value - exact value| for query variant 0
+    // |list-scan value - exact value| for query variant 0.  An fp8 plane takes
+    // the same bound with the fp8 records of the query (|x8|, |x - x8|, |x|)
+    // and of the plane: the truncation term |x8| max|ry| + |rx| max|y8| + |rx|
+    // max|ry| and the accumulation term 2.04 d u |x8| max|y8| (the bf16 MFMA
+    // sums exact products of the codes' values in fp32, and the scaling by
+    // 2^-(e_p + e_q) is exact unless the result is subnormal: at most 2^-149
+    // more, inside the bound's 1e-30 absolute slack).
     const bool prune = !first_stage && !(flags & MQVS_F_RERANK_ALL) && ix->yrec && k < R;
     float *craw = nullptr, *ibq = nullptr;
     if (prune) {
         craw = (float *)ws.craw.get(sizeof(float) * (size_t)nq * R);
         ibq = (float *)ws.ibq.get(sizeof(float) * (size_t)nq);
         if (split) qdelta = (float *)ws.qdelta.get(sizeof(float) * (size_t)nq);
-        if (!qrec0) {
+        if (fp8) {
+            qrec0 = q8rec;
+        } else if (!qrec0) {
             qrec0 = (float *)ws.crec.get(sizeof(float) * kMxRec * (size_t)nq);
             launch_to_hi(qvars, nq, d, (int64_t)maxv * qstride, ix->dpad, 1, round_up(nq, 16), nullptr, qrec0, nullptr, s);
         }
@@ -1134,15 +1211,16 @@ static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int 
     int64_t *dstats = nullptr;
     if (first_stage) {
         dstats = list_pass(ws.fine, ix->plane, ix->perm, ix->pnorm, ix->list_off, ix->nlist, ix->npos, ix->max_list,
-                           ix->dpad, ix->metric, qhi, qnorms, nq, probes, nprobe, dfilter, dexists, R, dids,
+                           ix->dpad, ix->metric, fp8 ? q8 : qhi, qnorms, nq, probes, nprobe, dfilter, dexists, R, dids,
                            seg->row_offset, ddist, tev ? ws.ev : nullptr, s, false, nullptr, pstats,
-                           &stats_per_query);
+                           &stats_per_query, fp8 ? &f8 : nullptr);
         MQVS_HIP(hipEventRecord(ws.ev[5], s));
     } else {
         int64_t *crow = (int64_t *)ws.rows.get(sizeof(int64_t) * (size_t)nq * R);
         dstats = list_pass(ws.fine, ix->plane, ix->perm, ix->pnorm, ix->list_off, ix->nlist, ix->npos, ix->max_list,
-                           ix->dpad, ix->metric, qhi, qnorms, nq, probes, nprobe, dfilter, dexists, R, crow, 0,
-                           nullptr, tev ? ws.ev : nullptr, s, false, craw, pstats, &stats_per_query);
+                           ix->dpad, ix->metric, fp8 ? q8 : qhi, qnorms, nq, probes, nprobe, dfilter, dexists, R, crow, 0,
+                           nullptr, tev ? ws.ev : nullptr, s, false, craw, pstats, &stats_per_query,
+                           fp8 ? &f8 : nullptr);
         // ---- exact re-rank (needs the whole variant chain)
         if (split) {
             MQVS_HIP(hipStreamWaitEvent(s, ws.join, 0));
@@ -1525,7 +1603,8 @@ struct BlobHeader {  // little-endian, as the host is
     uint64_t n, nlist;
     uint32_t alpha_bits, np95;
     uint64_t fingerprint;
-    uint8_t reserved[8];
+    uint32_t plane_fmt;  // MQVS_INDEX_PLANE_* (zero on a binary index)
+    uint8_t reserved[4];
 };
 static_assert(sizeof(BlobHeader) == MQVS_INDEX_BLOB_HEADER_BYTES, "the documented header");
 
@@ -1614,6 +1693,7 @@ static size_t save_impl(mqvs_index *ix, uint8_t *out, size_t cap) {
     std::memcpy(&hd.alpha_bits, &ix->alpha, 4);
     hd.np95 = (uint32_t)ix->np95;
     hd.fingerprint = segment_fingerprint(seg, s);
+    hd.plane_fmt = ix->binary ? 0u : (uint32_t)ix->plane_fmt;
 
     // ---- the content: header, centroid table, canonical assignment
     TmpBuf cont((size_t)content), asg(sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1));
@@ -1678,7 +1758,8 @@ static void check_blob_header(const BlobHeader &hd) {
                               : (hd.metric == MQVS_METRIC_HAMMING || hd.metric == MQVS_METRIC_JACCARD);
     if ((!fl && !bi) || !metric_ok || hd.nlist < 1 || hd.nlist > (1u << 20) || hd.n >= ((uint64_t)1 << 31) ||
         (hd.n > 0 && hd.nlist > hd.n) || !(alpha >= 1.0f && alpha <= 4.0f) || hd.np95 > (uint32_t)kSortCap ||
-        hd.dim == 0 || hd.dim > (1u << 24) || (bi && hd.dim % 8))
+        hd.dim == 0 || hd.dim > (1u << 24) || (bi && hd.dim % 8) ||
+        (hd.plane_fmt != MQVS_INDEX_PLANE_BF16 && (bi || hd.plane_fmt != MQVS_INDEX_PLANE_FP8)))
         fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: malformed header");
 }
 
@@ -1762,6 +1843,7 @@ static mqvs_index *load_impl(mqvs_segment *seg, const uint8_t *blob, size_t byte
         } else {
             ix->coarse_metric = ix->metric == MQVS_METRIC_L2 ? MQVS_METRIC_L2 : kMetricIpRaw;
             ix->dpad = round_up(seg->d, kBfK);
+            ix->plane_fmt = (int)hd.plane_fmt;
             ix->cent = segment_from_device((const float *)(c + sizeof(hd)), L, seg->d,
                                            ix->metric == MQVS_METRIC_L2 ? MQVS_METRIC_L2 : MQVS_METRIC_IP, s);
         }
@@ -1843,6 +1925,18 @@ int mqvs_index_info(mqvs_index_t idx, mqvs_index_info_t *out) {
         out->dim = idx->seg->d;
         out->hbm_bytes = idx->bytes;
         out->build_ms = idx->build_ms;
+    });
+}
+
+int mqvs_index_plane(mqvs_index_t idx, int32_t *format, size_t *plane_bytes) {
+    return guarded([&] {
+        if (!idx) fail(MQVS_ERR_BAD_ARGUMENTS, "null index");
+        if (idx->binary) fail(MQVS_ERR_LOGICAL, "binary index: it has no float list plane");
+        const bool fp8 = idx->plane_fmt == MQVS_INDEX_PLANE_FP8;
+        if (format) *format = idx->plane_fmt;
+        if (plane_bytes)
+            *plane_bytes = (size_t)idx->npos * (size_t)idx->dpad * (fp8 ? 1 : 2) +
+                           (fp8 ? sizeof(int16_t) * (size_t)idx->npos : 0);
     });
 }
 

@@ -18,6 +18,10 @@
 //   k_ivf_select  per query: radix-select the num_reorder best approximate
 //                 values, ordered compaction, bitonic sort in LDS
 // then the exact fp32 re-rank (k_rerank_ids, kernels_rerank.hip).
+//
+// An index built with plane=fp8 keeps the plane as e4m3fn codes at 1 B per
+// element instead (k_to_fp8; k_ivf_scan_fp8 widens them to bf16 in registers);
+// plan, select and re-rank are the same.
 #include <cstdlib>
 
 #include "mqvs_internal.h"
@@ -184,7 +188,7 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_lists_blk(IvfParams p) {
     if (t == 0 && blockIdx.x == 0) {
         *p.nitems = (int)t1;
         p.stats[1] = t1;
-        p.stats[2] = t2 * p.dpad * 2;
+        p.stats[2] = t2 * p.dpad * p.esize;
         p.stats[3] = (int64_t)p.nq * p.nprobe;
     }
 }
@@ -328,7 +332,7 @@ __global__ __launch_bounds__(kPlanThreads) void k_plan_small(IvfParams p) {
         *p.nitems = (int)nitems;
         p.stats[0] = total;
         p.stats[1] = nitems;
-        p.stats[2] = (int64_t)s_rows * p.dpad * 2;
+        p.stats[2] = (int64_t)s_rows * p.dpad * p.esize;
         p.stats[3] = E;
     }
 }
@@ -361,7 +365,7 @@ __global__ __launch_bounds__(256) void k_plan_dense(IvfParams p, int64_t npos) {
         *p.nitems = L * G * NC;
         p.stats[0] = (int64_t)p.nq * npos;
         p.stats[1] = (int64_t)L * G * NC;
-        p.stats[2] = (int64_t)G * npos * p.dpad * 2;
+        p.stats[2] = (int64_t)G * npos * p.dpad * p.esize;
         p.stats[3] = E;
     }
 }
@@ -397,7 +401,7 @@ __device__ inline void ivf_pair_stats(const IvfRegions &g, int q, int64_t T, boo
     int64_t *o = g.stats + 4 * (int64_t)q;
     o[0] = T;
     o[1] = items;
-    o[2] = T * g.dpad * 2;
+    o[2] = T * g.dpad * g.esize;
     o[3] = pairs;
 }
 
@@ -567,6 +571,207 @@ __global__ __launch_bounds__(256) void k_ivf_scan(IvfParams p) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float raw = acc[j][r];
+                    if (METRIC == MQVS_METRIC_L2) raw = (s_qn[16 * j + l16] + pn[r]) - 2.0f * raw;
+                    out[r].raw = rr[r] >= 0 ? raw : __builtin_nanf("");
+                    out[r].row = rr[r] >= 0 ? (uint32_t)rr[r] : 0xFFFFFFFFu;
+                }
+                uint4 *dst = reinterpret_cast<uint4 *>(p.cand + s_base[16 * j + l16] + lp);
+                dst[0] = *reinterpret_cast<const uint4 *>(&out[0]);
+                dst[1] = *reinterpret_cast<const uint4 *>(&out[2]);
+            }
+        }
+    }
+}
+
+// The same scan over an fp8 list plane (mqvs_index_build, plane=fp8): OCP
+// e4m3fn codes with one scale exponent per position and per query.  Work
+// items, prefetch sequence, non-temporal plane loads and the epilogue are
+// k_ivf_scan's; only the bytes streamed halve.  The plane is blocked [npos /
+// 16][dpad / 64][16][64] bytes, so a fragment load of a wave still reads one
+// contiguous KiB: lane (l16, c) takes bytes [16c, 16c + 16) of row l16 of a
+// 64-column window and feeds them as two k-steps (columns 16c .. 16c + 7 and
+// 16c + 8 .. 16c + 15); the query tile in LDS is read in the same order (32
+// contiguous bytes per lane and window), so both operands of a k-step hold
+// the same columns.  kIvfWin8 windows per group: the bytes in flight per lane
+// of the bf16 scan's group.
+//
+// The products are summed by the bf16 MFMA, not by v_mfma_f32_16x16x32_fp8_fp8:
+// every e4m3 value is a bf16 value, so the codes are widened in registers
+// (v_cvt_scalef32_pk_bf16_fp8 with scale 1: 8 VALU instructions per lane and
+// window beside 2 QB MFMAs, in a kernel bound by HBM) and the query tile holds
+// the queries' scaled codes as bf16.  The fp8 MFMA sums its 32 products in a
+// window of about 13 bits under the largest one (measured on an MI355X,
+// tools/fp8_mfma_probe.hip: up to 2^-10.7 of the largest product per
+// instruction on random codes; 2^16 + 2^-7 gives 2^16) -- the accumulation
+// term of k_query_bound, and a first stage pinned to 2.04 d u sum |p|, need
+// the fp32 sum the bf16 MFMA gives.  The accumulator then holds the sum of
+// the code products (each exact in fp32); the approximate inner product is
+// that sum times 2^-(e_p + e_q), scaled in one step (v_ldexp_f32: the product
+// of the two scales can leave the fp32 range where the result does not).  A
+// result that is not finite is reported as NaN, which the select ranks first
+// before a re-rank (the exact value decides) and leaves out of a first-stage
+// result.
+constexpr int kIvfWin8 = 8;
+typedef uint32_t ivf_u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 ivf_bf16x2 __attribute__((ext_vector_type(2)));
+
+// 8 e4m3fn codes (two dwords) as the 8 bf16 values of an MFMA fragment
+__device__ __forceinline__ ivf_bf16x8 ivf_widen8(uint32_t lo, uint32_t hi) {
+    ivf_u32x4 w;
+    w[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false));
+    w[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true));
+    w[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false));
+    w[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true));
+    return __builtin_bit_cast(ivf_bf16x8, w);
+}
+
+template <int METRIC, int QB>
+__global__ __launch_bounds__(256) void k_ivf_scan_fp8(IvfParams p) {
+    constexpr int QG = 16 * QB;
+    auto ldp = [](const uint8_t *a) __attribute__((always_inline)) {
+        return __builtin_nontemporal_load(reinterpret_cast<const ivf_u32x4 *>(a));
+    };
+    extern __shared__ __attribute__((aligned(16))) unsigned char qtile[];  // QG x (2 dpad + 16) B
+    __shared__ int s_ent[QG];
+    __shared__ int64_t s_base[QG];
+    __shared__ float s_qn[QG];
+    const int64_t qstr = 2 * p.dpad + 16;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int l16 = lane & 15, c = lane >> 4;
+    const int nitems = p.pair_stride ? p.nq * p.nprobe * p.pair_nch : *p.nitems;
+    const int cpr = (int)(p.dpad / 8);  // 16-B chunks per query row
+    const int ngrp = (int)((p.dpad / 64 + kIvfWin8 - 1) / kIvfWin8);
+    for (int it = blockIdx.x; it < nitems; it += gridDim.x) {
+        int l, g, chk, pe = -1;
+        if (p.pair_stride) {
+            // pair mode, slice-major (see k_ivf_scan)
+            const int E = p.nq * p.nprobe;
+            chk = it / E;
+            pe = it - chk * E;
+            g = 0;
+            const int64_t ll = p.probes[pe];
+            if (ll < 0 || ll >= p.nlist) continue;  // (uniform over the workgroup)
+            l = (int)ll;
+            if ((int64_t)chk * p.chunk >= p.list_off[l + 1] - p.list_off[l]) continue;
+        } else {
+            l = p.item_list[it];
+            g = p.item_grp[it];
+            chk = p.item_chk[it];
+        }
+        const int64_t pos0 = p.list_off[l];
+        const int cb = p.chunk / 16;  // 16-position blocks per work item
+        const int nb = (int)min<int64_t>((p.list_off[l + 1] - pos0) / 16, (int64_t)(chk + 1) * cb);
+        const int b0 = chk * cb + w;
+        const int nsteps = b0 < nb ? (nb - b0 + 3) / 4 * ngrp : 0;
+        // a block's 64-column window is one KiB piece: row l16 at 64 l16
+        const uint8_t *rp0 = p.plane8 + ((pos0 >> 4) + (int64_t)b0) * 16 * p.dpad + l16 * 64 + c * 16;
+        const int64_t bstride = 4 * 16 * p.dpad;  // 4 blocks on
+        auto load = [&](int st, ivf_u32x4 *dst) {
+            const int bi = st / ngrp, grp = st - bi * ngrp;
+            const uint8_t *rp = rp0 + bi * bstride;
+#pragma unroll
+            for (int u = 0; u < kIvfWin8; ++u) {
+                const int64_t kw = ((int64_t)grp * kIvfWin8 + u) * 64;
+                if (kw < p.dpad) dst[u] = ldp(rp + (kw >> 6) * 1024);
+            }
+        };
+        // the first step's rows are requested before the query tile is staged
+        ivf_u32x4 cur[kIvfWin8], nxt[kIvfWin8];
+        if (nsteps > 0) load(0, cur);
+        const int cnt = p.pair_stride ? 1 : min(QG, p.lcount[l] - g * QG);
+        __syncthreads();  // the previous item's readers are done with qtile
+        if (threadIdx.x < QG) {
+            const int j = threadIdx.x;
+            int e = -1;
+            int64_t base = 0;
+            if (p.pair_stride) {
+                if (j == 0) {
+                    e = pe;
+                    const int q = e / p.nprobe, r = e - q * p.nprobe;
+                    base = (int64_t)q * p.pair_stride;
+                    for (int r2 = 0; r2 < r; ++r2) {
+                        const int64_t l2 = p.probes[(int64_t)q * p.nprobe + r2];
+                        if (l2 >= 0 && l2 < p.nlist) base += p.list_off[l2 + 1] - p.list_off[l2];
+                    }
+                }
+            } else {
+                e = j < cnt ? p.lq[p.lstart[l] + (int64_t)g * QG + j] : -1;
+                base = e >= 0 ? p.qstart[e / p.nprobe] + p.qbase[e] : 0;
+            }
+            s_ent[j] = e;
+            s_base[j] = base;
+            s_qn[j] = (e >= 0 && METRIC == MQVS_METRIC_L2) ? p.qnorm[e / p.nprobe] : 0.f;
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < QG * cpr; i += 256) {
+            const int j = i / cpr, cc = i - j * cpr;
+            const int e = s_ent[j];
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (e >= 0) v = reinterpret_cast<const uint4 *>(p.q_hi + (int64_t)(e / p.nprobe) * p.dpad)[cc];
+            *reinterpret_cast<uint4 *>(qtile + j * qstr + cc * 16) = v;
+        }
+        __syncthreads();
+        const unsigned char *qp = qtile + l16 * qstr + c * 32;
+        int ent[QB];
+#pragma unroll
+        for (int j = 0; j < QB; ++j) ent[j] = s_ent[16 * j + l16];
+        int qe[QB];  // the slots' query scale exponents
+#pragma unroll
+        for (int j = 0; j < QB; ++j) qe[j] = ent[j] >= 0 ? (int)p.qexp[ent[j] / p.nprobe] : 0;
+        ivf_f32x4 acc[QB];
+        int32_t rows[4];
+        float pn[4];
+        int pe8[4];
+        for (int st = 0; st < nsteps; ++st) {
+            const int bi = st / ngrp, grp = st - bi * ngrp;
+            const int64_t lp = (int64_t)(b0 + 4 * bi) * 16 + 4 * c;
+            if (grp == 0) {
+#pragma unroll
+                for (int j = 0; j < QB; ++j) acc[j] = ivf_f32x4{0.f, 0.f, 0.f, 0.f};
+                // the block's position records, ahead of the next step's loads
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    rows[r] = p.perm[pos0 + lp + r];
+                    pn[r] = METRIC == MQVS_METRIC_L2 ? p.pnorm[pos0 + lp + r] : 0.f;
+                    pe8[r] = p.pscale[pos0 + lp + r];
+                }
+            }
+            if (st + 1 < nsteps) load(st + 1, nxt);
+#pragma unroll
+            for (int u = 0; u < kIvfWin8; ++u) {
+                const int64_t kw = ((int64_t)grp * kIvfWin8 + u) * 64;
+                if (kw < p.dpad) {
+                    const ivf_bf16x8 a0 = ivf_widen8(cur[u][0], cur[u][1]), a1 = ivf_widen8(cur[u][2], cur[u][3]);
+#pragma unroll
+                    for (int j = 0; j < QB; ++j) {
+                        const unsigned char *qj = qp + 16 * j * qstr + 2 * kw;
+                        const ivf_bf16x8 q0 = *reinterpret_cast<const ivf_bf16x8 *>(qj);
+                        const ivf_bf16x8 q1 = *reinterpret_cast<const ivf_bf16x8 *>(qj + 16);
+                        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, q0, acc[j], 0, 0, 0);
+                        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, q1, acc[j], 0, 0, 0);
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kIvfWin8; ++u) cur[u] = nxt[u];
+            if (grp != ngrp - 1) continue;
+            // C: lane (l16, c) holds rows 4c..4c+3 of the block for query slot 16 j + l16
+            int32_t rr[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                int32_t row = rows[r];
+                if (row >= 0 && p.filter && !bit_test(p.filter, row)) row = -1;
+                if (row >= 0 && p.exists && !bit_test(p.exists, row)) row = -1;
+                rr[r] = row;
+            }
+#pragma unroll
+            for (int j = 0; j < QB; ++j) {
+                if (ent[j] < 0) continue;
+                Cand out[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float raw = ldexpf(acc[j][r], -(pe8[r] + qe[j]));
+                    if (!(fabsf(raw) < __builtin_inff())) raw = __builtin_nanf("");
                     if (METRIC == MQVS_METRIC_L2) raw = (s_qn[16 * j + l16] + pn[r]) - 2.0f * raw;
                     out[r].raw = rr[r] >= 0 ? raw : __builtin_nanf("");
                     out[r].row = rr[r] >= 0 ? (uint32_t)rr[r] : 0xFFFFFFFFu;
@@ -854,6 +1059,134 @@ __global__ __launch_bounds__(256) void k_ivf_pack(const float *rows, const float
     }
 }
 
+// ---- fp8 list plane (plane=fp8) --------------------------------------------
+
+// the value of an e4m3fn code (exact)
+__device__ inline float e4m3_value(uint32_t c) {
+    const uint32_t e = (c >> 3) & 15u, m = c & 7u;
+    float v;
+    if (e == 15u && m == 7u)
+        v = __builtin_nanf("");
+    else if (e == 0u)
+        v = (float)m * 0x1p-9f;
+    else
+        v = __builtin_bit_cast(float, ((e + 120u) << 23) | (m << 20));  // 2^(e - 7) (1 + m / 8)
+    return (c & 0x80u) ? -v : v;
+}
+
+// The quantiser of include/mqvs.h (mqvs_index_build, plane=fp8), one wave per
+// vector: amax and its frexp exponent E, scale exponent e = 8 - E (0 for a zero
+// or non-finite amax), codes = e4m3fn(x_i 2^e) by the hardware conversion
+// (round to nearest even; scaled magnitudes of a finite vector lie under 256;
+// a scaled value that is not within 448 -- a vector with a non-finite element
+// only -- is stored as the NaN code).  Norm records as k_to_hi's, with v8 =
+// the de-scaled codes: [0] |v8|, [1] |v - v8|, [6] |v|, summed in fp64 (the
+// first two in the scaled domain, where codes and residuals are exact) and
+// rounded up; their maxima over the vectors that are not padding (maxrec) are
+// the list plane's record for k_query_bound.  A non-finite element makes the
+// sums, and so the maxima, non-finite (NaN counts as +inf), which turns the
+// re-rank's bound pruning off.
+//
+// Output: codes (the list plane, blocked [m / 16][dpad / 64][16][64] bytes), or
+// hi (queries: the scaled codes' values as bf16, which holds every e4m3 value,
+// row-major [m][dpad]: the B operand of k_ivf_scan_fp8).
+__global__ __launch_bounds__(256) void k_to_fp8(const float *src, int64_t sld, int d, const int32_t *perm, int64_t m,
+                                                int64_t dpad, uint8_t *codes, uint16_t *hi, int16_t *expo,
+                                                const float *norms, float *pnorm, float *rec, float *maxrec) {
+    __shared__ unsigned smax[4][3];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    unsigned mx[3] = {0u, 0u, 0u};  // running maxima (bit patterns of non-negative floats; NaN -> +inf)
+    for (int64_t v = (int64_t)blockIdx.x * 4 + w; v < m; v += (int64_t)gridDim.x * 4) {
+        const int64_t row = perm ? (int64_t)perm[v] : v;
+        const float *x = row >= 0 ? src + row * sld : nullptr;
+        float amax = 0.f;
+        if (x)
+            for (int i = lane; i < d; i += 64) {
+                const float a = fabsf(x[i]);
+                amax = fmaxf(amax, a == a ? a : __builtin_inff());
+            }
+        for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
+        int e = 0;
+        if (amax > 0.f && amax < __builtin_inff()) {
+            // amax = f 2^E, f in [0.5, 1) (subnormals included)
+            const uint32_t bits = __builtin_bit_cast(uint32_t, amax), ex = bits >> 23;
+            const int E = ex ? (int)ex - 126 : -149 + (32 - __clz((int)(bits & 0x7FFFFFu)));
+            e = 8 - E;
+        }
+        uint8_t *out = codes ? codes + (v >> 4) * 16 * dpad + (v & 15) * 64 : nullptr;
+        double nx = 0, nh = 0, nr = 0;
+        for (int64_t i = 4 * lane; i < dpad; i += 256) {
+            float xv[4], sv[4];
+            bool in[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                xv[j] = (x && i + j < d) ? x[i + j] : 0.f;
+                sv[j] = ldexpf(xv[j], e);
+                in[j] = fabsf(sv[j]) <= 448.f;
+            }
+            int pk = __builtin_amdgcn_cvt_pk_fp8_f32(in[0] ? sv[0] : 0.f, in[1] ? sv[1] : 0.f, 0, false);
+            pk = __builtin_amdgcn_cvt_pk_fp8_f32(in[2] ? sv[2] : 0.f, in[3] ? sv[3] : 0.f, pk, true);
+            uint32_t word = 0;
+            uint16_t hb[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint32_t code = ((uint32_t)pk >> (8 * j)) & 0xFFu;
+                if (!in[j]) code = 0x7Fu | ((__builtin_bit_cast(uint32_t, sv[j]) >> 24) & 0x80u);
+                word |= code << (8 * j);
+                const float hf = e4m3_value(code);
+                hb[j] = (uint16_t)(__builtin_bit_cast(uint32_t, hf) >> 16);  // exact: 4 significant bits
+                const double hv = (double)hf, rv = (double)sv[j] - hv;
+                nx += (double)xv[j] * xv[j];
+                nh += hv * hv;
+                nr += rv * rv;
+            }
+            if (out) *reinterpret_cast<uint32_t *>(out + (i >> 6) * 1024 + (i & 63)) = word;
+            if (hi)
+                *reinterpret_cast<uint2 *>(hi + v * dpad + i) =
+                    make_uint2(hb[0] | ((uint32_t)hb[1] << 16), hb[2] | ((uint32_t)hb[3] << 16));
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            nx += __shfl_xor(nx, off);
+            nh += __shfl_xor(nh, off);
+            nr += __shfl_xor(nr, off);
+        }
+        if (lane == 0) {
+            expo[v] = (int16_t)e;
+            if (pnorm) pnorm[v] = row >= 0 ? norms[row] : 0.f;
+        }
+        if (row < 0) continue;  // padding: no record
+        // (scaled sums back to the vector's units; rounded up)
+        const float r[kMxRec] = {(float)(ldexp(sqrt(nh), -e) * (1.0 + 1e-7)),
+                                 (float)(ldexp(sqrt(nr), -e) * (1.0 + 1e-7)),
+                                 0.f, 0.f, 0.f, 0.f,
+                                 (float)(sqrt(nx) * (1.0 + 1e-7)), 0.f};
+        if (rec && lane < kMxRec) {
+            float rv = 0.f;
+#pragma unroll
+            for (int t = 0; t < kMxRec; ++t)
+                if (lane == t) rv = r[t];
+            rec[v * kMxRec + lane] = rv;
+        }
+        const int slot[3] = {0, 1, 6};
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const float f = r[slot[t]];
+            const unsigned b = (f == f) ? __builtin_bit_cast(unsigned, f) : 0x7F800000u;
+            mx[t] = b > mx[t] ? b : mx[t];
+        }
+    }
+    if (!maxrec) return;
+    if (lane == 0)
+        for (int t = 0; t < 3; ++t) smax[w][t] = mx[t];
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int t = threadIdx.x;
+        unsigned b = smax[0][t];
+        for (int ww = 1; ww < 4; ++ww) b = smax[ww][t] > b ? smax[ww][t] : b;
+        atomicMax(reinterpret_cast<unsigned *>(maxrec) + (t == 2 ? 6 : t), b);
+    }
+}
+
 // dst[i] = src[idx[i]] (rows of d floats, source row stride src_ld; idx null = identity)
 __global__ __launch_bounds__(256) void k_gather_rows(const float *src, int64_t src_ld, int d, const int64_t *idx,
                                                      int64_t m, float *dst) {
@@ -947,7 +1280,43 @@ static void ivf_scan_t(const IvfParams &p, int metric, int grid, hipStream_t s) 
     }
 }
 
+template <int QB>
+static void ivf_scan_fp8_t(const IvfParams &p, int metric, int grid, hipStream_t s) {
+    const size_t lds = (size_t)16 * QB * (2 * p.dpad + 16);  // the bf16 scan's tile
+    if (ivf_scan_lds(16 * QB, p.dpad) > device_lds_bytes())
+        fail(MQVS_ERR_LOGICAL, "ivf scan: " + std::to_string(16 * QB) + "-query tile of " + std::to_string(p.dpad) +
+                                   " padded dimensions exceeds the workgroup's LDS");
+    if (lds > 65536) {
+        MQVS_HIP(hipFuncSetAttribute((const void *)k_ivf_scan_fp8<MQVS_METRIC_L2, QB>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        MQVS_HIP(hipFuncSetAttribute((const void *)k_ivf_scan_fp8<MQVS_METRIC_IP, QB>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        MQVS_HIP(hipFuncSetAttribute((const void *)k_ivf_scan_fp8<MQVS_METRIC_COSINE, QB>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    switch (metric) {
+        case MQVS_METRIC_L2:
+            hipLaunchKernelGGL((k_ivf_scan_fp8<MQVS_METRIC_L2, QB>), dim3(grid), dim3(256), lds, s, p);
+            break;
+        case MQVS_METRIC_IP:
+            hipLaunchKernelGGL((k_ivf_scan_fp8<MQVS_METRIC_IP, QB>), dim3(grid), dim3(256), lds, s, p);
+            break;
+        default:
+            hipLaunchKernelGGL((k_ivf_scan_fp8<MQVS_METRIC_COSINE, QB>), dim3(grid), dim3(256), lds, s, p);
+            break;
+    }
+}
+
 void launch_ivf_scan(const IvfParams &p, int metric, int grid, hipStream_t s) {
+    if (p.plane8) {
+        if (p.qg == 64)
+            ivf_scan_fp8_t<4>(p, metric, grid, s);
+        else if (p.qg == 32)
+            ivf_scan_fp8_t<2>(p, metric, grid, s);
+        else
+            ivf_scan_fp8_t<1>(p, metric, grid, s);
+        return;
+    }
     if (p.qg == 64)
         ivf_scan_t<4>(p, metric, grid, s);
     else if (p.qg == 32)
@@ -1016,6 +1385,15 @@ void launch_ivf_pack(const float *rows, const float *norms, int d, const int32_t
     const int64_t total = npos * (dpad / 8);
     const int grid = (int)std::min<int64_t>((total + 255) / 256, 65536);
     if (grid > 0) hipLaunchKernelGGL(k_ivf_pack, dim3(grid), dim3(256), 0, s, rows, norms, d, perm, npos, dpad, plane, pnorm);
+}
+
+void launch_to_fp8(const float *src, int64_t src_ld, int d, const int32_t *perm, int64_t m, int64_t dpad,
+                   uint8_t *codes, uint16_t *hi, int16_t *expo, const float *norms, float *pnorm, float *rec,
+                   float *maxrec, hipStream_t s) {
+    if (m <= 0) return;
+    const int64_t blocks = std::min<int64_t>((m + 3) / 4, (int64_t)device_cus() * 16);
+    hipLaunchKernelGGL(k_to_fp8, dim3((unsigned)blocks), dim3(256), 0, s, src, src_ld, d, perm, m, dpad, codes, hi,
+                       expo, norms, pnorm, rec, maxrec);
 }
 
 void launch_gather_rows(const float *src, int64_t src_ld, int d, const int64_t *idx, int64_t m, float *dst,

@@ -471,6 +471,12 @@ struct IvfParams {
     // region starts at q * pair_stride and holds its probes' lists back to back
     int64_t pair_stride;
     int pair_nch;
+    // fp8 list plane (plane8 non-null: k_ivf_scan_fp8; `plane` unused, q_hi
+    // holds the queries' scaled e4m3fn codes as bf16 values)
+    const uint8_t *plane8;    // e4m3fn codes, [npos/16][dpad/64][16][64] (k_to_fp8)
+    const int16_t *pscale;    // [npos] scale exponent e_p of each position
+    const int16_t *qexp;      // [nq] scale exponent e_q of each query
+    int esize;                // bytes per plane element: 2 (bf16) or 1 (fp8)
 };
 
 // The per-query candidate regions of a list pass, as the select reads them:
@@ -484,6 +490,7 @@ struct IvfRegions {
     const int64_t *probes = nullptr;
     const int64_t *list_off = nullptr;
     int64_t *stats = nullptr;  // pair mode: [nq][4] values, items, plane bytes, pairs per query
+    int esize = 2;             // bytes per plane element (the stats' plane bytes)
 };
 
 // LDS of one k_ivf_scan workgroup with qg-query work items: the query tile
@@ -508,6 +515,18 @@ void launch_ivf_select(const Cand *cand, const IvfRegions &rg, int nq, int R, in
                        float *out_raw = nullptr);
 void launch_ivf_pack(const float *rows, const float *norms, int d, const int32_t *perm, int64_t npos, int64_t dpad,
                      uint16_t *plane, float *pnorm, hipStream_t s);
+// fp8 (OCP e4m3fn) quantisation of m vectors with one power-of-two scale
+// each (the rule in include/mqvs.h, mqvs_index_build): vector v is row perm[v]
+// of src (perm null: row v; perm[v] < 0: a padding position, zero codes).
+// codes (optional): the list plane's [m/16][dpad/64][16][64] layout; hi
+// (optional): the scaled codes' values as bf16, row-major [m][dpad] (queries).
+// expo[v] = the scale exponent; pnorm (optional): the
+// row's norms[perm[v]]; rec (optional): [m][kMxRec] records [0] |v8|, [1] |v -
+// v8|, [6] |v| (v8 the de-scaled codes); maxrec (optional): their maxima over
+// the vectors that are not padding, non-finite for a non-finite vector.
+void launch_to_fp8(const float *src, int64_t src_ld, int d, const int32_t *perm, int64_t m, int64_t dpad,
+                   uint8_t *codes, uint16_t *hi, int16_t *expo, const float *norms, float *pnorm, float *rec,
+                   float *maxrec, hipStream_t s);
 void launch_gather_rows(const float *src, int64_t src_ld, int d, const int64_t *idx, int64_t m, float *dst,
                         hipStream_t s);
 constexpr int kCoarsePickMaxT = 64;  // core groups (and nprobe) of a coarse pick

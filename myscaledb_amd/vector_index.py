@@ -66,6 +66,14 @@ class VectorIndex:
         check(lib.mqvs_index_info(self._h, ctypes.byref(st)))
         return {f: getattr(st, f) for f, _ in _lib.IndexInfo._fields_}
 
+    def plane(self):
+        """The list plane (mqvs_index_plane): {"format": 0 bf16 | 1 fp8 (build
+        parameter ``plane``), "plane_bytes": its HBM bytes, scale array included}."""
+        fmt = ctypes.c_int32()
+        nbytes = ctypes.c_size_t()
+        check(lib.mqvs_index_plane(self._h, ctypes.byref(fmt), ctypes.byref(nbytes)))
+        return {"format": fmt.value, "plane_bytes": nbytes.value}
+
     def centroids(self):
         """The coarse step's centroid table, float32[nlist, dim]."""
         info = self.info()
