@@ -16,18 +16,12 @@
 //   re-normalised (spherical k-means).  Every row is then assigned to its
 //   nearest centroid; finish_index groups the rows by list on the device (row
 //   order within a list) and writes the lists back to back as a bf16 plane.
-// Save / load (mqvs_index_save, mqvs_index_load): centroids + each row's list
-//   behind a 64-byte header; the load ends in the same finish_index.
-// Search:
-//   coarse   FLAT search of the queries against the centroid segment, k =
-//            nprobe (L2 for L2 parts, raw inner product for IP and cosine)
-//   plan     (query, list) pairs grouped by list into 16-query work items
-//   scan     bf16 MFMA over each probed list (kernels_ivf.hip); an index built
-//            with plane=fp8 keeps e4m3fn codes there, widened in registers
-//   select   num_reorder best approximate values per query
-//   re-rank  exact fp32 distances of those rows (k_rerank_ids: the formula
-//            and cosine query variant of mqvs_search / mqvs_rerank), top-k by
-//            the reference order key
+// Save / load (mqvs_index_save, mqvs_index_load; index_blob.hip): centroids +
+//   each row's list behind a 64-byte header; the load ends in the same
+//   finish_index.
+// Search of a float index: index_search.hip.  This file holds the build, the
+// list count's auto-tuning, the binary index and the C glue; index_internal.h
+// what the three files share.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,52 +33,7 @@
 #include <chrono>
 #include <vector>
 
-#include "mqvs_internal.h"
-
-struct mqvs_index {
-    mqvs_segment *seg = nullptr;   // borrowed: the caller keeps the segment alive
-    int metric = 0;                // search metric (L2, IP or Cosine)
-    int coarse_metric = 0;         // L2 or kMetricIpRaw
-    int64_t nlist = 0;
-    int64_t npos = 0;
-    int64_t max_list = 0;
-    int64_t rows_indexed = 0;
-    int64_t dpad = 0;
-    float alpha = 3.0f;            // default search alpha
-    mqvs_segment *cent = nullptr;  // centroid segment (k-means assignment during the build)
-    uint16_t *plane = nullptr;     // bf16 rows in list order, [npos/16][dpad/32][16][32] (k_ivf_pack)
-    // plane=fp8 (plane_fmt MQVS_INDEX_PLANE_FP8; `plane` is then null): e4m3fn
-    // codes in list order, [npos/16][dpad/64][16][64], and each position's
-    // scale exponent (k_to_fp8)
-    int plane_fmt = MQVS_INDEX_PLANE_BF16;
-    uint8_t *plane8 = nullptr;
-    int16_t *pscale = nullptr;
-    int32_t *perm = nullptr;       // [npos] row of each position, -1 = padding
-    float *pnorm = nullptr;        // [npos] |y|^2
-    int64_t *list_off = nullptr;   // [nlist+1]
-    float *yrec = nullptr;         // [kMxRec] maxima over the rows of |bf16(y)|, |y - bf16(y)|, |y| (the
-                                   // re-rank's bound pruning: k_query_bound's segment record; fp8: of
-                                   // the de-scaled codes, over the indexed positions)
-    // coarse quantizer in the same list layout: the centroids in chunks of
-    // kCoarseChunk (every query probes every chunk), bf16 plane + |c|^2
-    int64_t cnl = 0, cnpos = 0, cmax = 0;
-    uint16_t *cplane = nullptr;
-    int32_t *cperm = nullptr;
-    float *cpnorm = nullptr;
-    int64_t *clist_off = nullptr;
-    // decoupled part (VIWithMeta::row_ids_map): old part row -> row id in the
-    // decoupled part, applied to every result (transferToNewRowIds)
-    uint64_t *row_ids_map = nullptr;
-    int64_t row_ids_len = 0;
-    size_t bytes = 0;
-    double build_ms = 0.0;
-    int np95 = 0;                  // nprobe measured to reach recall@10 0.95 on the build's sample (0: not measured)
-    // binary index (BINARYMSTG; kernels_bivf.hip): metric is Hamming or
-    // Jaccard, perm / list_off as above (no padding positions)
-    bool binary = false;
-    uint32_t *bplane = nullptr;    // [npos][code_words] codes in list order
-    uint32_t *bcent = nullptr;     // [nlist][code_words] k-majority centroids
-};
+#include "index_internal.h"
 
 namespace mqvs {
 mqvs_segment *index_segment(mqvs_index *idx) { return idx ? idx->seg : nullptr; }
@@ -92,79 +41,7 @@ mqvs_segment *index_segment(mqvs_index *idx) { return idx ? idx->seg : nullptr; 
 
 namespace mqvs {
 
-static thread_local mqvs_index_search_stats g_istats{};
-constexpr int64_t kCoarseChunk = 256;  // centroids per coarse "list"
-constexpr int64_t kCoarseFlatLists = 16384;  // more lists: the coarse step is a FLAT search
-
-// plan / scan / select buffers of one list pass
-struct ListBufs {
-    GBuf lcount, lfill, lstart, lq, items, grp, chk, nitems, qbase, qstart, cand, stats, large;
-    size_t release() {
-        size_t b = 0;
-        for (GBuf *x : {&lcount, &lfill, &lstart, &lq, &items, &grp, &chk, &nitems, &qbase, &qstart, &cand, &stats,
-                        &large}) {
-            b += x->cap;
-            x->release();
-        }
-        return b;
-    }
-};
-
-// The scratch of a thread's index searches.  Every buffer is a GBuf: it grows
-// through the thread's FLAT workspace gate (WsScope in search_index_impl), so
-// concurrent index searches share the process-wide HBM budget with FLAT
-// scans, and an idle thread's index scratch is trimmed with its workspace.
-struct IndexWorkspace final : WsExt {
-    hipEvent_t ev[6] = {};
-    // the cosine variant chain runs on `side` between fork and join (created
-    // on the workspace's device: index_workspace is called under its guard)
-    hipEvent_t fork = nullptr, join = nullptr;
-    hipStream_t side = nullptr;
-    int64_t *host = nullptr;  // pinned: the search's stats [4] and status word (one sync, no staging copies)
-    CallIO io;  // staged inputs and outputs of host-pointer searches
-    GBuf qvars, qnorms, qmu, qlam, status, qhi, probes, cprobes, rows, ord, dmap, dwords, pdist, cqhi, gmax, crec, cbq,
-        craw, ibq, qdelta, pstats, q8, q8exp, q8rec;
-    ListBufs coarse, fine;
-    // WsExt: the owner is between calls (its workspace's `done` event passed:
-    // the main stream, which joins the side chain, has drained)
-    size_t free_scratch() override {
-        if (side) (void)hipStreamSynchronize(side);
-        size_t b = io.release();
-        for (GBuf *x : {&qvars, &qnorms, &qmu, &qlam, &status, &qhi, &probes, &cprobes, &rows, &ord, &dmap, &dwords,
-                        &pdist, &cqhi, &gmax, &crec, &cbq, &craw, &ibq, &qdelta, &pstats, &q8, &q8exp, &q8rec}) {
-            b += x->cap;
-            x->release();
-        }
-        return b + coarse.release() + fine.release();
-    }
-    void init() {
-        if (ev[0]) return;
-        for (auto &e : ev) MQVS_HIP(hipEventCreate(&e));
-        MQVS_HIP(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
-        MQVS_HIP(hipEventCreateWithFlags(&join, hipEventDisableTiming));
-        MQVS_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-        MQVS_HIP(hipHostMalloc((void **)&host, 8 * sizeof(int64_t), hipHostMallocDefault));
-    }
-    // after the last search's kernels (ev[5] ends every search, ASYNC ones
-    // included; the side stream's chain is joined before it)
-    // (the scratch is detached and freed first: ws_detach_ext)
-    void release() {
-        if (!ev[0]) return;
-        (void)hipEventSynchronize(ev[5]);
-        if (side) (void)hipStreamSynchronize(side);
-        for (auto &e : ev) {
-            (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-        (void)hipEventDestroy(fork);
-        (void)hipEventDestroy(join);
-        (void)hipStreamDestroy(side);
-        (void)hipHostFree(host);
-        fork = join = nullptr;
-        side = nullptr;
-        host = nullptr;
-    }
-};
+thread_local mqvs_index_search_stats g_istats{};
 
 static thread_local std::map<int, IndexWorkspace> *g_iws = nullptr;
 
@@ -180,7 +57,7 @@ void index_thread_release() {
     g_iws->clear();
 }
 
-static IndexWorkspace &index_workspace(int device) {
+IndexWorkspace &index_workspace(int device) {
     if (!g_iws) g_iws = new std::map<int, IndexWorkspace>();  // leaked at exit on purpose
     IndexWorkspace &w = (*g_iws)[device];
     w.init();
@@ -189,7 +66,7 @@ static IndexWorkspace &index_workspace(int device) {
 
 
 // ---- Search::Parameters: "k=v,k=v" ----------------------------------------
-static std::map<std::string, std::string> parse_params(const char *s) {
+std::map<std::string, std::string> parse_params(const char *s) {
     std::map<std::string, std::string> out;
     if (!s) return out;
     std::string str(s);
@@ -215,7 +92,7 @@ static std::map<std::string, std::string> parse_params(const char *s) {
     return out;
 }
 
-static double num_param(const std::map<std::string, std::string> &m, const std::string &key, double dflt,
+double num_param(const std::map<std::string, std::string> &m, const std::string &key, double dflt,
                         double lo, double hi) {
     auto it = m.find(key);
     if (it == m.end()) return dflt;
@@ -227,7 +104,7 @@ static double num_param(const std::map<std::string, std::string> &m, const std::
     return v;
 }
 
-static void check_keys(const std::map<std::string, std::string> &m, const std::vector<std::string> &valid,
+void check_keys(const std::map<std::string, std::string> &m, const std::vector<std::string> &valid,
                        const char *what) {
     for (auto &kv : m) {
         if (std::find(valid.begin(), valid.end(), kv.first) == valid.end()) {
@@ -241,7 +118,7 @@ static void check_keys(const std::map<std::string, std::string> &m, const std::v
 
 // nprobe for a search alpha: nprobe(3) = base, doubling per unit of alpha;
 // the base probes 1/256 of the lists and at least 4 lists and 4096 rows
-static int nprobe_of(const mqvs_index *ix, double alpha) {
+int nprobe_of(const mqvs_index *ix, double alpha) {
     const double rows = (double)std::max<int64_t>(ix->rows_indexed, 1);
     // (an index whose list count was chosen from its data knows the nprobe
     // that reached recall@10 0.95 on the build's sample: alpha 3 probes 1.5x
@@ -286,7 +163,7 @@ static void group_by_list(const std::vector<int64_t> &assign, int64_t L, int64_t
     }
 }
 
-static void free_index(mqvs_index *ix) {
+void free_index(mqvs_index *ix) {
     if (!ix) return;
     int cur = -1;
     (void)hipGetDevice(&cur);
@@ -301,38 +178,6 @@ static void free_index(mqvs_index *ix) {
     delete ix;
 }
 
-template <typename T>
-static T *dalloc(mqvs_index *ix, size_t count) {
-    T *p = nullptr;
-    const size_t bytes = sizeof(T) * std::max<size_t>(count, 1);
-    if (hipMalloc((void **)&p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        fail(MQVS_ERR_MEMORY_LIMIT, "HBM allocation of " + std::to_string(bytes) + " bytes failed");
-    }
-    ix->bytes += bytes;
-    return p;
-}
-
-struct TmpBuf {
-    void *p = nullptr;
-    explicit TmpBuf(size_t bytes) {
-        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) {
-            (void)hipGetLastError();
-            fail(MQVS_ERR_MEMORY_LIMIT, "HBM allocation of " + std::to_string(bytes) + " bytes failed");
-        }
-    }
-    ~TmpBuf() {
-        if (p) (void)hipFree(p);
-    }
-    template <typename T>
-    T *as() const {
-        return (T *)p;
-    }
-};
-
-static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int k, const char *params,
-                              const uint8_t *filter, const uint8_t *exists, int64_t *out_ids, float *out_dist,
-                              uint32_t flags, hipStream_t user_stream, int formula_nq, int maxv_hint = 0);
 static mqvs_index *build_auto(mqvs_segment *seg, const char *index_type, const char *params);
 constexpr int64_t kAutoNlistMinRows = 1 << 20;  // smaller parts take the default list count
 
@@ -340,7 +185,7 @@ static mqvs_index *build_binary_impl(mqvs_segment *seg, const char *params);
 
 // the list scan keeps a tile of at least 16 bf16 queries in LDS
 // (ivf_scan_lds): rows too wide for that cannot be searched
-static void check_index_width(mqvs_segment *seg) {
+void check_index_width(mqvs_segment *seg) {
     const int d = seg->d;
     DeviceGuard guard(seg->device);
     const int64_t lim = device_lds_bytes();
@@ -364,7 +209,7 @@ static void check_index_width(mqvs_segment *seg) {
 // range-checked by the kernel that first reads it, and the verdict is read
 // before anything is sized by or indexed with it: from a blob (from_blob) a
 // bad value is the blob's fault, from a build the device's.
-static void finish_index(mqvs_index *ix, const int32_t *assign, bool from_blob, hipStream_t s) {
+void finish_index(mqvs_index *ix, const int32_t *assign, bool from_blob, hipStream_t s) {
     mqvs_segment *seg = ix->seg;
     const int64_t n = seg->n, L = ix->nlist;
     const int d = seg->d;
@@ -777,542 +622,6 @@ static mqvs_index *build_auto(mqvs_segment *seg, const char *index_type, const c
     return a;
 }
 
-// ---- search -----------------------------------------------------------------
-
-// One list pass: plan + bf16 MFMA scan + select of nq queries over a list
-// layout (the index's lists, or the coarse quantizer's centroid chunks).
-// probes[nq][nprobe] are list ids; out: the R best rows per query by the
-// approximate distance (+ id_offset; with out_approx, ids and approximate
-// distances for a first-stage result).  ev (optional): events 2..4 after
-// plan, scan and select.  pair_stats ([nq][4] words; null: no pair mode):
-// few pairs per list take pair mode (no plan; the select writes each query's
-// stats there).  Returns the stats words of the pass; *per_query: whether
-// they are pair mode's per-query rows.  f8 (an fp8 index's fine pass): the
-// plane's codes and scale exponents and the queries' exponents; `plane` is
-// unused and qhi holds the queries' scaled codes as bf16 values.
-struct ListFp8 {
-    const uint8_t *plane8;
-    const int16_t *pscale;
-    const int16_t *qexp;
-};
-static int64_t *list_pass(ListBufs &b, const uint16_t *plane, const int32_t *perm, const float *pnorm,
-                          const int64_t *list_off, int64_t nlist, int64_t npos, int64_t max_list, int64_t dpad,
-                          int metric, const uint16_t *qhi, const float *qnorm, int nq, const int64_t *probes,
-                          int nprobe, const uint8_t *filter, const uint8_t *exists, int R, int64_t *out_rows,
-                          int64_t id_offset, float *out_approx, hipEvent_t *ev, hipStream_t s, bool dense = false,
-                          float *out_raw = nullptr, int64_t *pair_stats = nullptr, bool *per_query = nullptr,
-                          const ListFp8 *f8 = nullptr) {
-    if (per_query) *per_query = false;
-    const int64_t E = (int64_t)nq * nprobe;
-    IvfParams p{};
-    p.plane = plane;
-    p.perm = perm;
-    p.pnorm = pnorm;
-    p.list_off = list_off;
-    p.nlist = (int)nlist;
-    p.dpad = dpad;
-    p.nq = nq;
-    p.nprobe = nprobe;
-    p.probes = probes;
-    p.q_hi = qhi;
-    p.qnorm = qnorm;
-    p.filter = filter;
-    p.exists = exists;
-    p.esize = 2;
-    if (f8) {
-        p.plane8 = f8->plane8;
-        p.pscale = f8->pscale;
-        p.qexp = f8->qexp;
-        p.esize = 1;
-    }
-    p.lcount = (int *)b.lcount.get(sizeof(int) * nlist);
-    p.lfill = (int *)b.lfill.get(sizeof(int) * nlist);
-    p.lstart = (int64_t *)b.lstart.get(sizeof(int64_t) * nlist);
-    p.lq = (int *)b.lq.get(sizeof(int) * E);
-    // 32-query work items when lists are probed by many queries (each A
-    // fragment then feeds two MFMAs)
-    // (64-query items, QB = 4, measured slower on the dense coarse pass at
-    // d = 768: its 99 KiB LDS tile leaves one workgroup per CU)
-    // Lists probed by very many queries (IVF-hostile data at large nprobe):
-    // 64-query items halve the list re-reads again (10M x 768, nq 1000,
-    // nprobe 512 = 51 queries per list: 14.4 -> 12.3 ms; at 13 per list
-    // they are slower, tools/index_qg_ab.py).
-    p.qg = (!dense && E >= 40 * nlist) ? 64 : (dense || E >= 24 * nlist) ? 32 : 16;
-    if (const char *e = tune_env("MQVS_IVF_QG")) {  // A/B knob (tools/ab_split.py style)
-        const int v = std::atoi(e);
-        if (!dense && (v == 16 || v == 32 || v == 64)) p.qg = v;
-    }
-    // wide rows: the largest of that size and its smaller siblings whose query
-    // tile fits a workgroup's LDS (64 up to dpad 1216, 32 up to 2496, 16 up to
-    // 5056 with 160 KiB; the dense plan groups by whatever p.qg is).  The
-    // build refuses wider rows, so something fits.
-    p.qg = ivf_fit_qg(p.qg, dpad, device_lds_bytes());
-    // (p.qg sizes the work items below; the build's own check keeps this from happening)
-    if (p.qg == 0) fail(MQVS_ERR_LOGICAL, "list scan: no query tile fits the workgroup's LDS");
-    // work items = sum over probed lists of groups x 512-position slices
-    // list positions per work item (a multiple of 64): 8 x the item's queries,
-    // so the query tile stays a fixed share of the bytes an item reads (round
-    // 5: 128 for 16-query items, 512 before -- the item setup's chain of
-    // dependent loads was a large part of a 256-position list's scan; mode 3
-    // nprobe 1 scan 0.139 -> 0.117 ms, profiles/r05/index_scan/)
-    p.chunk = dense ? kIvfChunk : std::max(64, tune_int("MQVS_IVF_CHUNK", 8 * p.qg) / 64 * 64);
-    // Pair mode: with about one query per probed list the plan groups
-    // nothing; it only orders the pairs (six launches over every list: ~43 us
-    // at 39063 lists, nq 1000, nprobe 1).  Instead every (pair, slice) is a
-    // work item of its own, each query's region a fixed stride.  Lists probed
-    // by several queries are then read once per query (mode 2 at nprobe 1:
-    // ~10 % of its list bytes twice).
-    const bool pairs = pair_stats && !dense && p.qg == 16 && 16 * E <= nlist && max_list > 0 &&
-                       (double)nq * nprobe * (max_list / p.chunk + 1) < 2e9 && tune_int("MQVS_IVF_PAIR", 1) == 1;
-    if (pairs) {
-        p.pair_stride = (int64_t)nprobe * max_list;
-        p.pair_nch = (int)((max_list + p.chunk - 1) / p.chunk);
-        p.stats = pair_stats;
-        p.cand = (Cand *)b.cand.get(sizeof(Cand) * (size_t)std::max<int64_t>((int64_t)nq * p.pair_stride, 1));
-        if (ev) MQVS_HIP(hipEventRecord(ev[2], s));
-        launch_ivf_scan(p, metric, tune_int("MQVS_IVF_GRID", 4096), s);
-        MQVS_HIP(hipGetLastError());
-        if (ev) MQVS_HIP(hipEventRecord(ev[3], s));
-        IvfRegions rg;
-        rg.stride = p.pair_stride;
-        rg.nprobe = nprobe;
-        rg.nlist = (int)nlist;
-        rg.chunk = p.chunk;
-        rg.dpad = dpad;
-        rg.esize = p.esize;
-        rg.probes = probes;
-        rg.list_off = list_off;
-        rg.stats = pair_stats;
-        const int64_t expect = (int64_t)((double)nprobe * npos / std::max<int64_t>(nlist, 1) * 1.5);
-        uint4 *gscr = R > kSortCap ? (uint4 *)b.large.get(sizeof(uint4) * 2 * (size_t)R * nq) : nullptr;
-        launch_ivf_select(p.cand, rg, nq, R, metric, out_rows, id_offset, out_approx, expect, s, gscr, out_raw);
-        MQVS_HIP(hipGetLastError());
-        if (ev) MQVS_HIP(hipEventRecord(ev[4], s));
-        if (per_query) *per_query = true;
-        return pair_stats;
-    }
-    const int64_t max_items = (E / p.qg + std::min<int64_t>(E, nlist)) * (max_list / p.chunk + 1);
-    p.item_list = (int *)b.items.get(sizeof(int) * max_items);
-    p.item_grp = (int *)b.grp.get(sizeof(int) * max_items);
-    p.item_chk = (int *)b.chk.get(sizeof(int) * max_items);
-    p.nitems = (int *)b.nitems.get(sizeof(int) * 4);
-    p.qbase = (int64_t *)b.qbase.get(sizeof(int64_t) * E);
-    p.qstart = (int64_t *)b.qstart.get(sizeof(int64_t) * (nq + 1));
-    // a query's region is at most min(nprobe * longest list, every position)
-    const int64_t cap = (int64_t)nq * std::min<int64_t>((int64_t)nprobe * max_list, npos);
-    p.cand = (Cand *)b.cand.get(sizeof(Cand) * (size_t)std::max<int64_t>(cap, 1));
-    const int64_t plan_wgs = (nlist + 4095) / 4096;  // k_plan_lists_* workgroups (>= 4096 lists each)
-    p.stats = (int64_t *)b.stats.get(sizeof(int64_t) * (8 + 3 * plan_wgs));
-    p.bsum = p.stats + 8;
-    if (dense)
-        launch_ivf_plan_dense(p, npos, s);
-    else
-        launch_ivf_plan(p, s);
-    MQVS_HIP(hipGetLastError());
-    if (ev) MQVS_HIP(hipEventRecord(ev[2], s));
-    // (a workgroup per work item up to 4096: ~2900 items at nq 1000, nprobe 1)
-    launch_ivf_scan(p, metric, dense ? 1024 : tune_int("MQVS_IVF_GRID", 4096), s);
-    MQVS_HIP(hipGetLastError());
-    if (ev) MQVS_HIP(hipEventRecord(ev[3], s));
-    const int64_t expect = dense ? npos : (int64_t)((double)nprobe * npos / std::max<int64_t>(nlist, 1) * 1.5);
-    // R above kSortCap: the select sorts through 2 R records of scratch per query
-    uint4 *gscr = R > kSortCap ? (uint4 *)b.large.get(sizeof(uint4) * 2 * (size_t)R * nq) : nullptr;
-    IvfRegions rg;
-    rg.qstart = p.qstart;
-    launch_ivf_select(p.cand, rg, nq, R, metric, out_rows, id_offset, out_approx, expect, s, gscr, out_raw);
-    MQVS_HIP(hipGetLastError());
-    if (ev) MQVS_HIP(hipEventRecord(ev[4], s));
-    return p.stats;
-}
-
-// mqvs_index_probes sets this for the duration of one search: the coarse
-// step's probes[nq][nprobe] are copied there and the search ends
-static thread_local int64_t *t_probes_out = nullptr;
-
-// formula_nq: the call's batch size, which selects the exact re-rank's
-// distance formula (0: nq; query sub-batches keep the call's, see search.hip)
-static void search_index_impl(mqvs_index *ix, const float *queries, int nq, int k, const char *params,
-                              const uint8_t *filter, const uint8_t *exists, int64_t *out_ids, float *out_dist,
-                              uint32_t flags, hipStream_t user_stream, int formula_nq, int maxv_hint) {
-    const int fnq = formula_nq > 0 ? formula_nq : nq;
-    check_search_args(ix, "index", ix && ix->binary ? "binary index: search it with mqvs_index_search_binary" : nullptr,
-                      nq, k, queries, out_ids, out_dist);
-    const auto pm = parse_params(params);
-    check_keys(pm, {"alpha", "nprobe", "num_reorder"}, "search");
-    const bool first_stage = flags & MQVS_F_FIRST_STAGE;
-    const double alpha = num_param(pm, "alpha", ix->alpha, 1.0, 4.0);
-    const int nprobe = pm.count("nprobe")
-                           ? (int)num_param(pm, "nprobe", 1, 1, (double)std::min<int64_t>(ix->nlist, kSortCap))
-                           : nprobe_of(ix, alpha);
-    // num_reorder up to kSortCap sorts in LDS; above it (k > 2048 by default,
-    // up to kLargeCap) through global scratch
-    const int R = first_stage ? k
-                              : (int)num_param(pm, "num_reorder",
-                                               (double)std::min(k > kSortCap / 2 ? kLargeCap : kSortCap, std::max(2 * k, 64)),
-                                               (double)std::max(k, 1), (double)kLargeCap);
-    mqvs_index_search_stats st{};
-    st.nq = nq;
-    st.k = k;
-    st.nprobe = nprobe;
-    st.num_reorder = R;
-    g_istats = st;
-    if (nq == 0 || k == 0) return;
-    if (R > kSortCap) {
-        // the select and the re-rank each take 2 R records of scratch per
-        // query: query sub-batches of <= 1 GB of it
-        const int qb = (int)std::max<int64_t>(1, (int64_t)scratch_budget() / 16 / (2 * (int64_t)R));
-        if (nq > qb) {
-            const int d = ix->seg->d;
-            for_query_batches(nq, qb, [&](int q0, int m) {
-                search_index_impl(ix, queries + (size_t)q0 * d, m, k, params, filter, exists,
-                                  out_ids + (size_t)q0 * k, out_dist + (size_t)q0 * k, flags, user_stream, fnq);
-            });
-            g_istats.nq = nq;
-            return;
-        }
-    }
-
-    mqvs_segment *seg = ix->seg;
-    DeviceGuard guard(seg->device);
-    IndexWorkspace &ws = index_workspace(seg->device);
-    // admission under the workspace budget; every scratch buffer below grows
-    // through its gate
-    WsScope scope(seg->device, &ws);
-    hipStream_t s = user_stream ? user_stream : thread_stream(seg->device);
-    scope.set_stream(s);
-    // the side stream's variant chain is joined into s on EVERY exit after it
-    // forks (an exception between fork and the re-rank's wait included), so
-    // the next search on this thread -- whose prep rewrites qvars and status
-    // on s -- and a trimmer waiting for s's completion see it finished
-    bool forked = false;
-    struct JoinGuard {
-        hipStream_t s;
-        hipEvent_t ev;
-        bool &on;
-        ~JoinGuard() {
-            if (on) (void)hipStreamWaitEvent(s, ev, 0);
-        }
-    } join_guard{s, ws.join, forked};
-    const bool dev = flags & MQVS_F_DEVICE_PTRS;
-    const int d = seg->d;
-    const bool cos = ix->metric == MQVS_METRIC_COSINE;
-    // per-stage timing events only when asked (MQVS_F_TIMING / mqvs_set_timing:
-    // ev[0..4]); ev[5] ends every search (the workspace trim waits on it)
-    const bool tev = timing_on(flags);
-    if (tev) MQVS_HIP(hipEventRecord(ws.ev[0], s));
-
-    const CallIO::In in =
-        ws.io.in(queries, sizeof(float) * (size_t)nq * d, filter, exists, (seg->n + 7) / 8, dev, s);
-    const float *dq = (const float *)in.queries;
-    const uint8_t *dfilter = in.filter, *dexists = in.exists;
-    const CallIO::Out out = ws.io.out((size_t)nq * k, dev, out_ids, out_dist);
-    int64_t *dids = out.ids;
-    float *ddist = out.dist;
-
-    // ---- query prep: cosine re-normalisation variants (the re-rank uses the
-    // row's chunk variant, as mqvs_search does), |q|^2.  The variant table
-    // starts at kMaxVariants per query with no host round trip; a chain that
-    // does not repeat within it on a part of more chunk ordinals (rare:
-    // small-integer data) is caught from the status word read at the end, and
-    // the search re-runs with the larger table (as mqvs_search does).  The
-    // table is not cleared: every variant a reader can select (ordinal < mu +
-    // lambda, or < maxv when the chain did not repeat) is written by the prep.
-    const int64_t ords = seg->row_offset / seg->granule + (seg->n + seg->granule - 1) / seg->granule;
-    const int maxv = cos ? (maxv_hint > 0 ? maxv_hint : kMaxVariants) : 1;
-    const int64_t qstride = round_up(d, 32);
-    float *qvars = (float *)ws.qvars.get(sizeof(float) * (size_t)nq * maxv * qstride);
-    float *qnorms = (float *)ws.qnorms.get(sizeof(float) * nq);
-    int *qmu = (int *)ws.qmu.get(sizeof(int) * nq);
-    int *qlam = (int *)ws.qlam.get(sizeof(int) * nq);
-    // [status 4 ints][pick overflow queries, candidates re-ranked: 2 x u64]
-    int *status = (int *)ws.status.get(sizeof(int) * 8);
-    launch_fill2(reinterpret_cast<uint32_t *>(status), 8, 0u, nullptr, 0, 0u, s);
-    auto *istat = reinterpret_cast<unsigned long long *>(status + 4);
-    // the fine pass's per-query stats in pair mode
-    auto *pstats = (int64_t *)ws.pstats.get(sizeof(int64_t) * 4 * (size_t)nq);
-    bool stats_per_query = false;
-    // Cosine: only variant 0 is needed before the exact re-rank (coarse step,
-    // list scan), so the rest of the chain -- a sequential fp32 sum per
-    // normalisation, up to kMaxVariants of them: 60-130 us at nq 1000 -- runs
-    // on the side stream meanwhile and is joined before the re-rank.
-    const bool split = cos && !first_stage;
-    launch_query_prep(dq, nq, d, cos ? MQVS_METRIC_COSINE : MQVS_METRIC_L2, ix->metric == MQVS_METRIC_L2, qvars, maxv,
-                      qnorms, qmu, qlam, status, s, split ? 1 : 0);
-    MQVS_HIP(hipGetLastError());
-    // The chain starts after the coarse step: beside the coarse batch kernel
-    // it slowed that kernel by ~20 us, beside the plan and the list scan it
-    // costs less (mode 3, nprobe 1: 0.564 -> 0.544 ms per batch,
-    // profiles/r04/index/fork_ab.jsonl).
-    float *qdelta = nullptr;  // cosine, pruned re-rank: the chain's variant spread (k_query_prep phase 2)
-    auto fork_chain = [&]() {
-        MQVS_HIP(hipEventRecord(ws.fork, s));
-        MQVS_HIP(hipStreamWaitEvent(ws.side, ws.fork, 0));
-        forked = true;
-        launch_query_prep(dq, nq, d, MQVS_METRIC_COSINE, false, qvars, maxv, qnorms, qmu, qlam, status, ws.side, 2,
-                          qdelta);
-        MQVS_HIP(hipGetLastError());
-        MQVS_HIP(hipEventRecord(ws.join, ws.side));
-    };
-    // variant 0 of every query in the list plane's format: bf16, or for an fp8
-    // plane the query's own e4m3fn codes (as the bf16 values the scan's MFMA
-    // takes) with its scale exponent and norm records (the bf16 rounding is
-    // then made only if the coarse step takes the centroid list pass)
-    const bool fp8 = ix->plane_fmt == MQVS_INDEX_PLANE_FP8;
-    uint16_t *qhi = (uint16_t *)ws.qhi.get(sizeof(uint16_t) * (size_t)nq * ix->dpad);
-    uint16_t *q8 = nullptr;
-    ListFp8 f8{};
-    float *q8rec = nullptr;
-    if (fp8) {
-        q8 = (uint16_t *)ws.q8.get(sizeof(uint16_t) * (size_t)nq * ix->dpad);
-        auto *q8exp = (int16_t *)ws.q8exp.get(sizeof(int16_t) * (size_t)nq);
-        q8rec = (float *)ws.q8rec.get(sizeof(float) * kMxRec * (size_t)nq);
-        launch_to_fp8(qvars, (int64_t)maxv * qstride, d, nullptr, nq, ix->dpad, nullptr, q8, q8exp, nullptr, nullptr,
-                      q8rec, nullptr, s);
-        f8 = ListFp8{ix->plane8, ix->pscale, q8exp};
-    } else {
-        launch_to_bf16(qvars, nq, d, (int64_t)maxv * qstride, qhi, ix->dpad, s);
-    }
-    MQVS_HIP(hipGetLastError());
-
-    // ---- coarse: the nprobe nearest centroids, by the same list pass over
-    // the centroid chunks (every query probes every chunk)
-    const int64_t *cprobes = nullptr;  // dense plan: probe r of every query is chunk r
-    int64_t *probes = (int64_t *)ws.probes.get(sizeof(int64_t) * (size_t)nq * nprobe);
-    // many lists: the FLAT batch search of the centroid segment (exact
-    // top-nprobe; ranking by the raw inner product for IP and cosine parts):
-    // 65536 lists, nq 1000: 1.26 -> 0.67 ms; few lists: the list pass over
-    // the centroid chunks (10000 lists: 0.28 ms vs 0.50, the FLAT path's
-    // fixed stages dominate; profiles/r03/index)
-    // Default (nprobe <= 64 and the centroid plane present): the batch kernel
-    // scores every (query, centroid) on bf16 and keeps the best of each
-    // 8-centroid group; the nprobe best groups per query (and any other
-    // group the bf16 bound cannot rule out) then get exact fp32 values and
-    // the nprobe best of those are the probes (k_coarse_pick).  65536 or 39063 lists at nq 1000: one batch-kernel
-    // launch and one pick instead of mqvs_search's whole pipeline.
-    bool picked = false;
-    const int cmode = tune_int("MQVS_IVF_COARSE", 2);
-    // (core groups of the pick: nprobe; any count keeps the probes exact,
-    // and more of them only score more centroids exactly,
-    // profiles/r05/pick/core_t_ab.jsonl)
-    float *qrec0 = nullptr;  // variant 0's norm records (the pick's bound; the re-rank pruning's)
-    if (nprobe >= ix->nlist) {
-        // every list is probed: nothing to rank, and nothing to lose -- the
-        // ranked forms never pick a centroid whose score is NaN (a NaN or
-        // infinite query; a centroid of a list that holds infinite rows)
-        launch_iota_probes(probes, nq, nprobe, s);
-        MQVS_HIP(hipGetLastError());
-        picked = true;
-    }
-    if (!picked && cmode == 2 && nprobe <= kCoarsePickMaxT && ix->cent && ix->cent->rows_hi && ix->cent->rows) {
-        mqvs_segment *cs = ix->cent;
-        const int64_t vpad = round_up(nq, 16);
-        auto *cq = (uint16_t *)ws.cqhi.get(sizeof(uint16_t) * (size_t)vpad * cs->dpad);
-        // (variant 0 of every query: the raw query, or the normalised one for
-        // cosine -- centroids of cosine parts are normalised: same ranking as
-        // the raw inner product)
-        // (with the variants' norm records: the pick's bf16 bound)
-        float *crec = (float *)ws.crec.get(sizeof(float) * kMxRec * (size_t)nq);
-        launch_to_hi(qvars, nq, d, (int64_t)maxv * qstride, cs->dpad, 1, vpad, cq, crec, nullptr, s);
-        qrec0 = crec;
-        MQVS_HIP(hipGetLastError());
-        ScanParams cp{};
-        cp.rows_hi = cs->rows_hi;
-        cp.row_norms = cs->norms;
-        cp.n = cs->n;
-        cp.d = d;
-        cp.dpad = cs->dpad;
-        cp.nq = nq;
-        cp.q_hi = cq;
-        cp.q_vpad = vpad;
-        cp.maxv = 1;
-        cp.qnorms = qnorms;
-        cp.chunk_rows = cs->granule;
-        cp.row_begin = 0;
-        cp.row_end = cs->n;
-        cp.tile_rows = 256;
-        cp.tiles = (cs->n + 255) / 256;
-        cp.tiles_per_chunk = 0;
-        // groups of 8 centroids: 32 per 256-row tile
-        const int64_t gld = round_up(32 * cp.tiles, 4);
-        cp.p4_gmax = (float *)ws.gmax.get(sizeof(float) * (size_t)nq * gld);
-        cp.p4_gld = gld;
-        if (launch_scan_p4_groups(cp, ix->coarse_metric, s)) {
-            MQVS_HIP(hipGetLastError());
-            // each query's bound on |bf16 group value - exact| (the direct
-            // formula's rounding terms: the larger of the two)
-            float *cbq = (float *)ws.cbq.get(sizeof(float) * (size_t)nq);
-            ScanParams bp = cp;
-            bp.blas_nq = 1;
-            launch_query_bound(bp, ix->coarse_metric, cs->ynorm_max, crec, cs->ynorm_max + 4, cbq, nullptr, s);
-            MQVS_HIP(hipGetLastError());
-            launch_coarse_pick(cp.p4_gmax, gld, 32 * cp.tiles, nprobe, nprobe, ix->coarse_metric, qvars,
-                               (int64_t)maxv * qstride, cs->rows, cs->norms, cs->n, d, cbq, qnorms, 3, nq, probes,
-                               istat, s);
-            MQVS_HIP(hipGetLastError());
-            picked = true;
-        }
-    }
-    if (picked) {
-    } else if (tune_int("MQVS_IVF_COARSE", ix->nlist > kCoarseFlatLists ? 1 : 0) == 1) {
-        float *pd = (float *)ws.pdist.get(sizeof(float) * (size_t)nq * nprobe);
-        search_internal(ix->cent, dq, nq, nprobe, ix->coarse_metric, nullptr, nullptr, probes, pd,
-                        MQVS_F_DEVICE_PTRS | (flags & MQVS_F_ASYNC), s);
-    } else {
-        if (fp8) {
-            launch_to_bf16(qvars, nq, d, (int64_t)maxv * qstride, qhi, ix->dpad, s);
-            MQVS_HIP(hipGetLastError());
-        }
-        list_pass(ws.coarse, ix->cplane, ix->cperm, ix->cpnorm, ix->clist_off, ix->cnl, ix->cnpos, ix->cmax,
-                  ix->dpad, ix->metric, qhi, qnorms, nq, cprobes, (int)ix->cnl, nullptr, nullptr, nprobe, probes, 0,
-                  nullptr, nullptr, s, true);
-    }
-    if (tev) MQVS_HIP(hipEventRecord(ws.ev[1], s));
-    if (t_probes_out) {
-        // mqvs_index_probes: the coarse step's lists, nothing after it
-        MQVS_HIP(hipMemcpyAsync(t_probes_out, probes, sizeof(int64_t) * (size_t)nq * nprobe, hipMemcpyDeviceToHost, s));
-        MQVS_HIP(hipMemcpyAsync(ws.host + 6, istat, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        host_wait(s);
-        g_istats.pick_overflow = (int32_t)ws.host[6];
-        return;
-    }
-    // ---- the re-rank's bound pruning (the candidates that cannot reach the
-    // exact top k are not re-ranked; same output): per query, the bound on
-    // |list-scan value - exact value| for query variant 0.  An fp8 plane takes
-    // the same bound with the fp8 records of the query (|x8|, |x - x8|, |x|)
-    // and of the plane: the truncation term |x8| max|ry| + |rx| max|y8| + |rx|
-    // max|ry| and the accumulation term 2.04 d u |x8| max|y8| (the bf16 MFMA
-    // sums exact products of the codes' values in fp32, and the scaling by
-    // 2^-(e_p + e_q) is exact unless the result is subnormal: at most 2^-149
-    // more, inside the bound's 1e-30 absolute slack).
-    const bool prune = !first_stage && !(flags & MQVS_F_RERANK_ALL) && ix->yrec && k < R;
-    float *craw = nullptr, *ibq = nullptr;
-    if (prune) {
-        craw = (float *)ws.craw.get(sizeof(float) * (size_t)nq * R);
-        ibq = (float *)ws.ibq.get(sizeof(float) * (size_t)nq);
-        if (split) qdelta = (float *)ws.qdelta.get(sizeof(float) * (size_t)nq);
-        if (fp8) {
-            qrec0 = q8rec;
-        } else if (!qrec0) {
-            qrec0 = (float *)ws.crec.get(sizeof(float) * kMxRec * (size_t)nq);
-            launch_to_hi(qvars, nq, d, (int64_t)maxv * qstride, ix->dpad, 1, round_up(nq, 16), nullptr, qrec0, nullptr, s);
-        }
-        ScanParams bp{};
-        bp.nq = nq;
-        bp.d = d;
-        bp.maxv = 1;
-        bp.qnorms = qnorms;
-        bp.blas_nq = fnq;
-        launch_query_bound(bp, ix->metric, seg->ynorm_max, qrec0, ix->yrec, ibq, nullptr, s);
-        MQVS_HIP(hipGetLastError());
-    }
-    if (split) fork_chain();
-
-    // ---- fine: the probed lists
-    int64_t *dstats = nullptr;
-    if (first_stage) {
-        dstats = list_pass(ws.fine, ix->plane, ix->perm, ix->pnorm, ix->list_off, ix->nlist, ix->npos, ix->max_list,
-                           ix->dpad, ix->metric, fp8 ? q8 : qhi, qnorms, nq, probes, nprobe, dfilter, dexists, R, dids,
-                           seg->row_offset, ddist, tev ? ws.ev : nullptr, s, false, nullptr, pstats,
-                           &stats_per_query, fp8 ? &f8 : nullptr);
-        MQVS_HIP(hipEventRecord(ws.ev[5], s));
-    } else {
-        int64_t *crow = (int64_t *)ws.rows.get(sizeof(int64_t) * (size_t)nq * R);
-        dstats = list_pass(ws.fine, ix->plane, ix->perm, ix->pnorm, ix->list_off, ix->nlist, ix->npos, ix->max_list,
-                           ix->dpad, ix->metric, fp8 ? q8 : qhi, qnorms, nq, probes, nprobe, dfilter, dexists, R, crow, 0,
-                           nullptr, tev ? ws.ev : nullptr, s, false, craw, pstats, &stats_per_query,
-                           fp8 ? &f8 : nullptr);
-        // ---- exact re-rank (needs the whole variant chain)
-        if (split) {
-            MQVS_HIP(hipStreamWaitEvent(s, ws.join, 0));
-            forked = false;
-        }
-        ScanParams rp{};
-        rp.rows = seg->rows;
-        rp.row_norms = seg->norms;
-        rp.n = seg->n;
-        rp.d = d;
-        rp.nq = nq;
-        rp.blas_nq = fnq;
-        rp.qvars = qvars;
-        rp.qnorms = qnorms;
-        rp.qmu = qmu;
-        rp.qlam = qlam;
-        rp.maxv = maxv;
-        rp.chunk_rows = seg->granule;
-        rp.chunk_ord = seg->chunk_ord;
-        if (cos && dfilter) {
-            // chunk ordinals as mqvs_search computes them under a PREWHERE
-            // filter (chunks without a selected row are never searched), so
-            // the re-rank picks the same cosine query variant per row
-            const int64_t nch = (seg->n + seg->granule - 1) / seg->granule;
-            int *o = (int *)ws.ord.get(sizeof(int) * std::max<int64_t>(nch, 1));
-            launch_chunk_ordinals(dfilter, seg->nonempty_bits, dexists, seg->n, seg->granule, 1, o, s);
-            MQVS_HIP(hipGetLastError());
-            rp.chunk_ord = o;
-        }
-        rp.ord_base = (int)(seg->row_offset / seg->granule);
-        rp.exists = dexists;
-        rp.filter = nullptr;  // the scan applied the filter; candidates pass it
-        rp.nonempty = seg->nonempty_bits;
-        uint4 *rscr = R > kSortCap ? (uint4 *)ws.fine.large.get(sizeof(uint4) * 2 * (size_t)R * nq) : nullptr;
-        RerankPrune pr{};
-        pr.count = istat + 1;
-        if (prune) {
-            pr.raw = craw;
-            pr.bq = ibq;
-            pr.ymax = seg->ynorm_max;
-            pr.qdelta = qdelta;
-        }
-        launch_rerank_ids(rp, ix->metric, crow, R, k, seg->row_offset, dids, ddist, rscr, s, pr);
-        MQVS_HIP(hipGetLastError());
-        MQVS_HIP(hipEventRecord(ws.ev[5], s));
-    }
-
-    // decoupled part: results in the new part's row ids (VIWithDataPart.cpp:938-943)
-    if (dev && ix->row_ids_map) launch_map_ids(dids, (int64_t)nq * k, ix->row_ids_map, s);
-    const bool async = dev && (flags & MQVS_F_ASYNC);
-    if (async) {
-        const bool variants_matter = !first_stage && ords > maxv;
-        launch_async_flags(nullptr, status, variants_matter ? 1 : 0, async_sticky(seg->device, s), s);
-        MQVS_HIP(hipGetLastError());
-        return;
-    }
-    int64_t *hs = ws.host;
-    int *hst = reinterpret_cast<int *>(ws.host + 4);
-    if (!dev) {
-        // (host outputs: copied before the final wait)
-        if (ix->row_ids_map) launch_map_ids(dids, (int64_t)nq * k, ix->row_ids_map, s);
-        ws.io.finish_begin(out, s);
-    }
-    launch_words_to_host(dstats, 4, status, 8, hs, hst, s, stats_per_query ? dstats : nullptr, nq);
-    MQVS_HIP(hipGetLastError());
-    host_wait(s);
-    if (const int want = first_stage ? 0 : check_variant_chain(*hst, ords, maxv)) {
-        search_index_impl(ix, queries, nq, k, params, filter, exists, out_ids, out_dist, flags, user_stream, fnq,
-                          want);
-        return;
-    }
-    ws.io.finish_end(out);
-    st.values = hs[0];
-    st.items = hs[1];
-    st.plane_bytes = hs[2];
-    st.pairs = hs[3];
-    st.pick_overflow = (int32_t)hs[6];  // (istat, copied with the status words)
-    st.reranked = hs[7];
-    float t[5] = {0, 0, 0, 0, 0}, tot = 0;
-    if (tev) {
-        for (int i = 0; i < 5; ++i) MQVS_HIP(hipEventElapsedTime(&t[i], ws.ev[i], ws.ev[i + 1]));
-        MQVS_HIP(hipEventElapsedTime(&tot, ws.ev[0], ws.ev[5]));
-    }
-    st.coarse_ms = t[0];
-    st.plan_ms = t[1];
-    st.scan_ms = t[2];
-    st.select_ms = t[3];
-    st.rerank_ms = t[4];
-    st.total_ms = tot;
-    g_istats = st;
-}
-
 // ---- binary index (BINARYMSTG seam) -------------------------------------------
 // The reference's index over FixedString(N) columns (KAT 00038); MSTG's code
 // is absent, so this is the library's own design: an inverted file over
@@ -1581,319 +890,6 @@ static void search_binary_index_impl(mqvs_index *ix, const uint8_t *queries, int
         st.total_ms = tot;
     }
     g_istats = st;
-}
-
-// ---- persistence: mqvs_index_save / mqvs_index_load -------------------------
-// A saved index is the five things a build decides -- centroids, each row's
-// list, nlist, alpha, np95 -- behind a 64-byte header, framed as a ClickHouse
-// CompressedWriteBuffer stream (include/mqvs.h has the layout byte by byte).
-// Everything else is derived again by finish_index.  The framing reuses the
-// column ingest's device code in both directions: launch_block_table and
-// launch_decode_blocks read it, launch_block_checksum verifies it and, through
-// hash_out, computes the checksums the writer stores.
-
-constexpr int64_t kBlobBlock = 1 << 20;  // payload bytes of the blocks mqvs_index_save writes
-constexpr int64_t kBlobFrame = 25;       // 16-B checksum + method byte + two UInt32 sizes
-constexpr char kBlobMagic[8] = {'M', 'Q', 'V', 'S', 'I', 'D', 'X', '\0'};
-constexpr int kFingerprintRows = 1024;
-
-struct BlobHeader {  // little-endian, as the host is
-    char magic[8];
-    uint32_t version, kind, metric, dim;
-    uint64_t n, nlist;
-    uint32_t alpha_bits, np95;
-    uint64_t fingerprint;
-    uint32_t plane_fmt;  // MQVS_INDEX_PLANE_* (zero on a binary index)
-    uint8_t reserved[4];
-};
-static_assert(sizeof(BlobHeader) == MQVS_INDEX_BLOB_HEADER_BYTES, "the documented header");
-
-static void put_block_header(uint8_t *h, uint32_t payload) {  // h: the 9 bytes after the checksum
-    const uint32_t csize = payload + 9;
-    h[0] = 0x02;
-    for (int i = 0; i < 4; ++i) {
-        h[1 + i] = (uint8_t)(csize >> (8 * i));
-        h[5 + i] = (uint8_t)(payload >> (8 * i));
-    }
-}
-
-static int64_t row_bytes_of(const mqvs_segment *seg) { return seg->binary ? seg->code_bytes : 4 * (int64_t)seg->d; }
-
-// The fingerprint of a segment's resident rows: S = min(n, 1024) rows, row
-// floor(i n / S) for i < S (the builds' sample rule), gathered back to back (a
-// float row as its d fp32 values as they are resident -- normalised for a
-// cosine segment --, a binary row as its dim_bits / 8 code bytes) and framed as
-// the payload of one method-NONE block; the fingerprint is the low 64 bits of
-// that block's CityHash128 checksum (k_block_checksum, one lane).  The rows are
-// read through seg->rows / seg->codes, which for rows moved to host memory is
-// the mapped address of the pinned copy.
-static uint64_t segment_fingerprint(mqvs_segment *seg, hipStream_t s) {
-    const int64_t n = seg->n, S = std::min<int64_t>(n, kFingerprintRows), rb = row_bytes_of(seg);
-    const int64_t len = S * rb;
-    // the block starts at byte 7, so that its payload starts at byte 32
-    TmpBuf buf(32 + (size_t)len + 16), tab(sizeof(IngestBlock)), out(sizeof(uint64_t) * 2 + sizeof(int) * 2);
-    uint8_t pre[32] = {};
-    put_block_header(pre + 23, (uint32_t)len);
-    IngestBlock b{};
-    b.src = 32;
-    b.csize = b.usize = (uint32_t)len;
-    b.method = 0x02;
-    MQVS_HIP(hipMemcpyAsync(buf.p, pre, 32, hipMemcpyHostToDevice, s));
-    MQVS_HIP(hipMemcpyAsync(tab.p, &b, sizeof(b), hipMemcpyHostToDevice, s));
-    MQVS_HIP(hipMemsetAsync(out.p, 0, sizeof(uint64_t) * 2 + sizeof(int) * 2, s));
-    std::vector<int64_t> idx64(S);
-    std::vector<int32_t> idx32(S);
-    for (int64_t i = 0; i < S; ++i) idx32[i] = (int32_t)(idx64[i] = (int64_t)((__int128)i * n / S));
-    TmpBuf didx(sizeof(int64_t) * std::max<int64_t>(S, 1)), wide(seg->binary ? sizeof(uint32_t) * (size_t)S * seg->code_words : 0);
-    if (S > 0 && seg->binary) {
-        MQVS_HIP(hipMemcpyAsync(didx.p, idx32.data(), sizeof(int32_t) * S, hipMemcpyHostToDevice, s));
-        launch_bivf_gather(seg->codes, seg->code_words, didx.as<int32_t>(), S, wide.as<uint32_t>(), s);
-        MQVS_HIP(hipMemcpy2DAsync(buf.as<uint8_t>() + 32, (size_t)rb, wide.p, (size_t)seg->code_words * 4, (size_t)rb,
-                                  (size_t)S, hipMemcpyDeviceToDevice, s));
-    } else if (S > 0) {
-        MQVS_HIP(hipMemcpyAsync(didx.p, idx64.data(), sizeof(int64_t) * S, hipMemcpyHostToDevice, s));
-        launch_gather_rows(seg->rows, seg->d, seg->d, didx.as<int64_t>(), S, (float *)(buf.as<uint8_t>() + 32), s);
-    }
-    uint64_t *hash = out.as<uint64_t>();
-    launch_block_checksum(buf.as<uint8_t>(), tab.as<IngestBlock>(), 1, 1, (int *)(hash + 2), hash, s);
-    MQVS_HIP(hipGetLastError());
-    uint64_t h[2] = {};
-    MQVS_HIP(hipMemcpyAsync(h, hash, sizeof(h), hipMemcpyDeviceToHost, s));
-    MQVS_HIP(hipStreamSynchronize(s));
-    return h[0];
-}
-
-static int64_t blob_content_bytes(const mqvs_index *ix) {
-    return (int64_t)sizeof(BlobHeader) + ix->nlist * row_bytes_of(ix->seg) + 4 * ix->seg->n;
-}
-
-static size_t blob_bytes(const mqvs_index *ix) {
-    const int64_t content = blob_content_bytes(ix);
-    return (size_t)(content + kBlobFrame * ((content + kBlobBlock - 1) / kBlobBlock));
-}
-
-static size_t save_impl(mqvs_index *ix, uint8_t *out, size_t cap) {
-    if (!ix || !out) fail(MQVS_ERR_BAD_ARGUMENTS, "null argument");
-    mqvs_segment *seg = ix->seg;
-    const int64_t n = seg->n, L = ix->nlist, rb = row_bytes_of(seg), cb = L * rb;
-    const int64_t content = blob_content_bytes(ix), nb = (content + kBlobBlock - 1) / kBlobBlock;
-    const size_t total = blob_bytes(ix);
-    if (cap < total)
-        fail(MQVS_ERR_BAD_ARGUMENTS, "output holds " + std::to_string(cap) + " bytes, " + std::to_string(total) + " needed");
-    DeviceGuard guard(seg->device);
-    hipStream_t s = thread_stream(seg->device);
-    BlobHeader hd{};
-    std::memcpy(hd.magic, kBlobMagic, 8);
-    hd.version = MQVS_INDEX_BLOB_VERSION;
-    hd.kind = ix->binary ? MQVS_INDEX_KIND_BINARY_IVF : MQVS_INDEX_KIND_FLOAT_IVF;
-    hd.metric = (uint32_t)ix->metric;
-    hd.dim = (uint32_t)seg->d;
-    hd.n = (uint64_t)n;
-    hd.nlist = (uint64_t)L;
-    std::memcpy(&hd.alpha_bits, &ix->alpha, 4);
-    hd.np95 = (uint32_t)ix->np95;
-    hd.fingerprint = segment_fingerprint(seg, s);
-    hd.plane_fmt = ix->binary ? 0u : (uint32_t)ix->plane_fmt;
-
-    // ---- the content: header, centroid table, canonical assignment
-    TmpBuf cont((size_t)content), asg(sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1));
-    uint8_t *c = cont.as<uint8_t>();
-    MQVS_HIP(hipMemcpyAsync(c, &hd, sizeof(hd), hipMemcpyHostToDevice, s));
-    if (ix->binary)
-        MQVS_HIP(hipMemcpy2DAsync(c + sizeof(hd), (size_t)rb, ix->bcent, (size_t)seg->code_words * 4, (size_t)rb,
-                                  (size_t)L, hipMemcpyDeviceToDevice, s));
-    else
-        MQVS_HIP(hipMemcpyAsync(c + sizeof(hd), ix->cent->rows, (size_t)cb, hipMemcpyDeviceToDevice, s));
-    if (n > 0) {
-        // the list of a position, scattered to its row; rows at no position: -1
-        MQVS_HIP(hipMemsetAsync(asg.p, 0xFF, sizeof(int32_t) * (size_t)n, s));
-        launch_grp_assign_of(ix->perm, ix->list_off, L, ix->npos, n, asg.as<int32_t>(), s);
-        MQVS_HIP(hipGetLastError());
-        MQVS_HIP(hipMemcpyAsync(c + sizeof(hd) + cb, asg.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
-    }
-    // ---- the frame: method NONE blocks of at most kBlobBlock bytes
-    TmpBuf framed(total), tab(sizeof(IngestBlock) * (size_t)nb), hashes(16 * (size_t)nb + 16);
-    std::vector<uint8_t> heads((size_t)nb * kBlobFrame, 0);
-    std::vector<IngestBlock> ht((size_t)nb);
-    for (int64_t i = 0; i < nb; ++i) {
-        const uint32_t len = (uint32_t)std::min(kBlobBlock, content - i * kBlobBlock);
-        put_block_header(heads.data() + i * kBlobFrame + 16, len);
-        ht[i].src = i * (kBlobBlock + kBlobFrame) + kBlobFrame;
-        ht[i].dst = i * kBlobBlock;
-        ht[i].csize = ht[i].usize = len;
-        ht[i].method = 0x02;
-        ht[i].pad = 0;
-    }
-    uint8_t *f = framed.as<uint8_t>();
-    const size_t pitch = (size_t)(kBlobBlock + kBlobFrame);
-    MQVS_HIP(hipMemcpy2DAsync(f, pitch, heads.data(), (size_t)kBlobFrame, (size_t)kBlobFrame, (size_t)nb,
-                              hipMemcpyHostToDevice, s));
-    const int64_t full = content / kBlobBlock, rest = content - full * kBlobBlock;
-    if (full > 0)
-        MQVS_HIP(hipMemcpy2DAsync(f + kBlobFrame, pitch, c, (size_t)kBlobBlock, (size_t)kBlobBlock, (size_t)full,
-                                  hipMemcpyDeviceToDevice, s));
-    if (rest > 0)
-        MQVS_HIP(hipMemcpyAsync(f + full * pitch + kBlobFrame, c + full * kBlobBlock, (size_t)rest,
-                                hipMemcpyDeviceToDevice, s));
-    MQVS_HIP(hipMemcpyAsync(tab.p, ht.data(), sizeof(IngestBlock) * (size_t)nb, hipMemcpyHostToDevice, s));
-    uint64_t *hash = hashes.as<uint64_t>();
-    // (the verdict word of the checksum pass is not read: the stored checksums are still zero)
-    launch_block_checksum(f, tab.as<IngestBlock>(), nb, 1, (int *)(hash + 2 * nb), hash, s);
-    MQVS_HIP(hipGetLastError());
-    MQVS_HIP(hipMemcpy2DAsync(f, pitch, hash, 16, 16, (size_t)nb, hipMemcpyDeviceToDevice, s));
-    MQVS_HIP(hipMemcpyAsync(out, f, total, hipMemcpyDeviceToHost, s));
-    MQVS_HIP(hipStreamSynchronize(s));
-    return total;
-}
-
-// the header of a decoded blob; throws what the error table of include/mqvs.h names
-static void check_blob_header(const BlobHeader &hd) {
-    if (std::memcmp(hd.magic, kBlobMagic, 8) != 0) fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: bad magic");
-    if (hd.version != MQVS_INDEX_BLOB_VERSION)
-        fail(MQVS_ERR_NOT_IMPLEMENTED, "index blob: format version " + std::to_string(hd.version) + " is not implemented");
-    float alpha;
-    std::memcpy(&alpha, &hd.alpha_bits, 4);
-    const bool fl = hd.kind == MQVS_INDEX_KIND_FLOAT_IVF, bi = hd.kind == MQVS_INDEX_KIND_BINARY_IVF;
-    const bool metric_ok = fl ? (hd.metric == MQVS_METRIC_L2 || hd.metric == MQVS_METRIC_IP || hd.metric == MQVS_METRIC_COSINE)
-                              : (hd.metric == MQVS_METRIC_HAMMING || hd.metric == MQVS_METRIC_JACCARD);
-    if ((!fl && !bi) || !metric_ok || hd.nlist < 1 || hd.nlist > (1u << 20) || hd.n >= ((uint64_t)1 << 31) ||
-        (hd.n > 0 && hd.nlist > hd.n) || !(alpha >= 1.0f && alpha <= 4.0f) || hd.np95 > (uint32_t)kSortCap ||
-        hd.dim == 0 || hd.dim > (1u << 24) || (bi && hd.dim % 8) ||
-        (hd.plane_fmt != MQVS_INDEX_PLANE_BF16 && (bi || hd.plane_fmt != MQVS_INDEX_PLANE_FP8)))
-        fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: malformed header");
-}
-
-static mqvs_index *load_impl(mqvs_segment *seg, const uint8_t *blob, size_t bytes) {
-    if (!seg || !blob) fail(MQVS_ERR_BAD_ARGUMENTS, "null argument");
-    if (bytes < (size_t)kBlobFrame + sizeof(BlobHeader)) fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: truncated");
-    const int64_t n = seg->n, rb = row_bytes_of(seg);
-    DeviceGuard guard(seg->device);
-    hipStream_t s = thread_stream(seg->device);
-    hipEvent_t e0, e1;
-    MQVS_HIP(hipEventCreate(&e0));
-    MQVS_HIP(hipEventCreate(&e1));
-    mqvs_index *ix = nullptr;
-    try {
-        MQVS_HIP(hipEventRecord(e0, s));
-        // ---- the block chain, its checksums, the decoded content
-        const int64_t maxb = (int64_t)bytes / kBlobFrame + 1;
-        TmpBuf dblob(bytes), tab(sizeof(IngestBlock) * (size_t)maxb), words(sizeof(int64_t) * 4);
-        MQVS_HIP(hipMemcpyAsync(dblob.p, blob, bytes, hipMemcpyHostToDevice, s));
-        launch_block_table(dblob.as<uint8_t>(), (int64_t)bytes, tab.as<IngestBlock>(), maxb, words.as<int64_t>(), s);
-        MQVS_HIP(hipGetLastError());
-        int64_t tb[3] = {};
-        MQVS_HIP(hipMemcpyAsync(tb, words.p, sizeof(tb), hipMemcpyDeviceToHost, s));
-        MQVS_HIP(hipStreamSynchronize(s));
-        // (no codec expands more than 256-fold: a larger claim is not allocated)
-        if (tb[2] || tb[1] < (int64_t)sizeof(BlobHeader) || tb[1] / 256 > (int64_t)bytes)
-            fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: truncated or malformed compressed block chain");
-        const int64_t nblk = tb[0], total = tb[1];
-        constexpr int kBadChecksum = 8;  // (the decode raises 4)
-        int *status = (int *)(words.as<int64_t>() + 3);
-        MQVS_HIP(hipMemsetAsync(status, 0, sizeof(int), s));
-        TmpBuf cont((size_t)total);
-        uint8_t *c = cont.as<uint8_t>();
-        launch_block_checksum(dblob.as<uint8_t>(), tab.as<IngestBlock>(), nblk, kBadChecksum, status, nullptr, s);
-        launch_decode_blocks(dblob.as<uint8_t>(), (int64_t)bytes, tab.as<IngestBlock>(), nblk, c, status, s);
-        MQVS_HIP(hipGetLastError());
-        int hstatus = 0;
-        BlobHeader hd{};
-        MQVS_HIP(hipMemcpyAsync(&hstatus, status, sizeof(int), hipMemcpyDeviceToHost, s));
-        MQVS_HIP(hipMemcpyAsync(&hd, c, sizeof(hd), hipMemcpyDeviceToHost, s));
-        MQVS_HIP(hipStreamSynchronize(s));
-        if (hstatus & kBadChecksum)
-            fail(MQVS_ERR_CHECKSUM, "Checksum doesn't match: corrupted data (index blob, CityHash128 of a compressed block)");
-        if (hstatus) fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: malformed LZ4 block (CANNOT_DECOMPRESS)");
-        // ---- the header against itself, then against the segment
-        check_blob_header(hd);
-        const bool binary = hd.kind == MQVS_INDEX_KIND_BINARY_IVF;
-        const int64_t L = (int64_t)hd.nlist;
-        const int64_t hrb = binary ? hd.dim / 8 : 4 * (int64_t)hd.dim, cb = L * hrb;
-        if (total != (int64_t)sizeof(BlobHeader) + cb + 4 * (int64_t)hd.n)
-            fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: " + std::to_string(total) + " bytes of content, the header implies " +
-                                              std::to_string((int64_t)sizeof(BlobHeader) + cb + 4 * (int64_t)hd.n));
-        if (binary != seg->binary)
-            fail(MQVS_ERR_LOGICAL, std::string("index blob: a ") + (binary ? "binary" : "Float32") + " index on a " +
-                                       (seg->binary ? "binary" : "Float32") + " segment");
-        if ((int64_t)hd.n != n || (int64_t)hd.dim != seg->d)
-            fail(MQVS_ERR_LOGICAL, "index blob: saved over " + std::to_string(hd.n) + " rows of dimension " +
-                                       std::to_string(hd.dim) + ", the segment has " + std::to_string(n) + " of " +
-                                       std::to_string(seg->d));
-        if (!binary && ((int)hd.metric == MQVS_METRIC_COSINE) != (seg->metric == MQVS_METRIC_COSINE))
-            fail(MQVS_ERR_LOGICAL, "segment was prepared for a different metric (cosine segments are normalised in HBM)");
-        if (!binary) check_index_width(seg);
-        if (hd.fingerprint != segment_fingerprint(seg, s))
-            fail(MQVS_ERR_LOGICAL, "index blob: saved over other rows than the segment's (fingerprint mismatch)");
-
-        // ---- the index
-        ix = new mqvs_index();
-        ix->seg = seg;
-        ix->binary = binary;
-        ix->metric = (int)hd.metric;
-        ix->nlist = L;
-        std::memcpy(&ix->alpha, &hd.alpha_bits, 4);
-        ix->np95 = (int)hd.np95;
-        if (binary) {
-            ix->coarse_metric = MQVS_METRIC_HAMMING;
-            const size_t cwb = (size_t)seg->code_words * 4;
-            ix->bcent = dalloc<uint32_t>(ix, (size_t)L * seg->code_words);
-            MQVS_HIP(hipMemsetAsync(ix->bcent, 0, cwb * (size_t)L, s));
-            MQVS_HIP(hipMemcpy2DAsync(ix->bcent, cwb, c + sizeof(hd), (size_t)rb, (size_t)rb, (size_t)L,
-                                      hipMemcpyDeviceToDevice, s));
-        } else {
-            ix->coarse_metric = ix->metric == MQVS_METRIC_L2 ? MQVS_METRIC_L2 : kMetricIpRaw;
-            ix->dpad = round_up(seg->d, kBfK);
-            ix->plane_fmt = (int)hd.plane_fmt;
-            ix->cent = segment_from_device((const float *)(c + sizeof(hd)), L, seg->d,
-                                           ix->metric == MQVS_METRIC_L2 ? MQVS_METRIC_L2 : MQVS_METRIC_IP, s);
-        }
-        // (the assignment follows a binary centroid table at any byte offset)
-        TmpBuf asg(sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1));
-        if (n > 0)
-            MQVS_HIP(hipMemcpyAsync(asg.p, c + sizeof(hd) + cb, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, s));
-        finish_index(ix, asg.as<int32_t>(), true, s);
-        MQVS_HIP(hipEventRecord(e1, s));
-        MQVS_HIP(hipStreamSynchronize(s));
-        float ms = 0.f;
-        MQVS_HIP(hipEventElapsedTime(&ms, e0, e1));
-        ix->build_ms = ms;
-        if (ix->cent) ix->bytes += ix->cent->bytes;
-    } catch (...) {
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        if (ix) free_index(ix);
-        throw;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return ix;
-}
-
-// host only: the header of a blob whose first block is stored (method NONE)
-static void blob_info_impl(const uint8_t *blob, size_t bytes, mqvs_index_blob_info_t *out) {
-    if (!blob || !out) fail(MQVS_ERR_BAD_ARGUMENTS, "null argument");
-    if (bytes < (size_t)kBlobFrame + sizeof(BlobHeader)) fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: truncated");
-    const uint8_t *h = blob + 16;
-    auto u32 = [](const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); };
-    if (h[0] == 0x82) fail(MQVS_ERR_NOT_IMPLEMENTED, "index blob: the first block is LZ4-compressed (load it, or decompress it first)");
-    const uint32_t csize = u32(h + 1), usize = u32(h + 5);
-    if (h[0] != 0x02 || csize < 9 || csize - 9 != usize || usize < sizeof(BlobHeader) || 16 + (size_t)csize > bytes)
-        fail(MQVS_ERR_ILLEGAL_COLUMN, "index blob: malformed first block");
-    BlobHeader hd;
-    std::memcpy(&hd, blob + kBlobFrame, sizeof(hd));
-    check_blob_header(hd);
-    std::memset(out, 0, sizeof(*out));
-    out->version = hd.version;
-    out->kind = hd.kind;
-    out->metric = (int32_t)hd.metric;
-    out->dim = (int32_t)hd.dim;
-    out->n = (int64_t)hd.n;
-    out->nlist = (int64_t)hd.nlist;
-    std::memcpy(&out->alpha, &hd.alpha_bits, 4);
-    out->np95 = (int32_t)hd.np95;
-    out->fingerprint = hd.fingerprint;
-    const int64_t hrb = hd.kind == MQVS_INDEX_KIND_BINARY_IVF ? hd.dim / 8 : 4 * (int64_t)hd.dim;
-    out->content_bytes = (uint64_t)((int64_t)sizeof(BlobHeader) + (int64_t)hd.nlist * hrb + 4 * (int64_t)hd.n);
 }
 
 }  // namespace mqvs

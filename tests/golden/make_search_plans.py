@@ -58,8 +58,47 @@ def cases():
 
 
 def index_cases():
+    """The two default builds, then float indexes of the main part built with an
+    explicit nlist (`build`: a deterministic build, shared by the cases that
+    name it), one case per branch of the index search's host code."""
+    def ix(build, nq, params, metric="L2", k=K, **kw):
+        return dict(kind="index", metric=metric, nq=nq, k=k, params=params, build=build, **kw)
+
     return [dict(kind="index", metric="L2", nq=8, k=K, params="nprobe=8"),
-            dict(kind="binary_index", metric="Hamming", nq=8, k=K, params="nprobe=8")]
+            dict(kind="binary_index", metric="Hamming", nq=8, k=K, params="nprobe=8"),
+            # pair mode (16 nq nprobe <= nlist), then the grouped plan with
+            # 16-, 32- (24 nlist <= nq nprobe < 40 nlist) and 64-query items
+            ix("nlist=4096", 8, "nprobe=8"),
+            ix("nlist=64", 8, "nprobe=8"),
+            ix("nlist=64", 200, "nprobe=8"),
+            ix("nlist=64", 200, "nprobe=16"),
+            # the coarse forms: every list probed (no ranking); nprobe above
+            # kCoarsePickMaxT: the centroid list pass, and above kCoarseFlatLists
+            # lists the FLAT search of the centroids (the pick: the cases above)
+            ix("nlist=64", 8, "nprobe=64"),
+            ix("nlist=256", 8, "nprobe=100"),
+            ix("nlist=20000,kmeans_iters=2", 8, "nprobe=100"),
+            # first stage only (the scan's own values), grouped and pair mode
+            ix("nlist=64", 8, "nprobe=8", first_stage=True),
+            ix("nlist=4096", 8, "nprobe=8", first_stage=True),
+            # num_reorder = k: nothing to prune; every candidate re-ranked
+            ix("nlist=64", 8, "nprobe=8,num_reorder=100"),
+            ix("nlist=64", 8, "nprobe=8", rerank_all=True),
+            ix("nlist=64", 8, "nprobe=8", sel=0.05),
+            # cosine: the variant chain forks to the side stream (several chunk
+            # ordinals: granule(metric)); under a filter the ordinals are recomputed
+            ix("nlist=64", 8, "nprobe=8", metric="Cosine"),
+            ix("nlist=64", 8, "nprobe=8", metric="Cosine", sel=0.05),
+            ix("nlist=64", 8, "nprobe=8", metric="IP"),
+            # fp8 list plane: pair mode, grouped, first stage of both, and the
+            # centroid list pass (which rounds the queries to bf16 after all)
+            ix("nlist=4096,plane=fp8", 8, "nprobe=8"),
+            ix("nlist=64,plane=fp8", 8, "nprobe=8"),
+            ix("nlist=4096,plane=fp8", 8, "nprobe=8", first_stage=True),
+            ix("nlist=64,plane=fp8", 8, "nprobe=8", first_stage=True),
+            ix("nlist=256,plane=fp8", 8, "nprobe=100"),
+            # large k (num_reorder above kSortCap): query sub-batches under a 4 MiB scratch budget
+            ix("nlist=64", 20, "nprobe=8", k=5000, scratch_budget=4 << 20)]
 
 
 def case_id(c):
@@ -68,6 +107,9 @@ def case_id(c):
         parts.append(f"sel{int(c['sel'] * 100)}")
     if c.get("exact"):
         parts.append("exact")
+    if c.get("build"):
+        # (index cases that name their build: the build, the search parameters and the flags)
+        parts += [c["build"], c["params"]] + [f for f in ("first_stage", "rerank_all") if c.get(f)]
     return "-".join(p for p in parts if p)
 
 
@@ -101,13 +143,14 @@ class Parts:
             self._segs["bin"] = self.mq.BinaryVectorScanSegment.from_codes(codes, metric="Hamming")
         return self._segs["bin"]
 
-    def index(self, kind):
-        if kind not in self._idx:
+    def index(self, kind, metric="L2", build=None):
+        key = (kind, metric, build)
+        if key not in self._idx:
             if kind == "index":
-                self._idx[kind] = self.mq.VectorIndex.build(self.float_seg("main", "L2"), "MSTG")
+                self._idx[key] = self.mq.VectorIndex.build(self.float_seg("main", metric), "MSTG", build)
             else:
-                self._idx[kind] = self.mq.BinaryVectorIndex.build(self.binary_seg(), "BINARYMSTG")
-        return self._idx[kind]
+                self._idx[key] = self.mq.BinaryVectorIndex.build(self.binary_seg(), "BINARYMSTG")
+        return self._idx[key]
 
     def free(self):
         for x in list(self._idx.values()) + list(self._segs.values()):
@@ -122,6 +165,22 @@ def float_queries(nq):
 
 def binary_queries(nq):
     return np.random.RandomState(0xB17 + nq).randint(0, 256, size=(nq, BIN_BITS // 8)).astype(np.uint8)
+
+
+def search_index_case(parts, c):
+    """The search of one index case; returns (ids, dist) as host arrays."""
+    from myscaledb_amd import vector_scan
+    idx = parts.index(c["kind"], c["metric"], c.get("build"))
+    if c["kind"] == "binary_index":
+        return idx.search(binary_queries(c["nq"]), c["k"], c["params"])
+    flt = None if c.get("sel") is None else selection(idx.segment.n, c["sel"])
+    prev = vector_scan.set_scratch_budget(c["scratch_budget"]) if c.get("scratch_budget") else None
+    try:
+        return idx.search(float_queries(c["nq"]), c["k"], c["params"], filter_bitmap=flt,
+                          first_stage_only=bool(c.get("first_stage")), rerank_all=bool(c.get("rerank_all")))
+    finally:
+        if prev is not None:
+            vector_scan.set_scratch_budget(prev)
 
 
 def run_case(parts, c):
@@ -142,9 +201,7 @@ def run_case(parts, c):
         parts.binary_seg().search(binary_queries(c["nq"]), c["k"])
         st = _lib.last_search_stats()
         return {f: int(st[f]) for f in SEARCH_FIELDS}
-    idx = parts.index(c["kind"])
-    q = float_queries(c["nq"]) if c["kind"] == "index" else binary_queries(c["nq"])
-    idx.search(q, c["k"], c["params"])
+    search_index_case(parts, c)
     st = _lib.last_index_stats()
     return {f: int(st[f]) for f in INDEX_FIELDS}
 
