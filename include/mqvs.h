@@ -86,6 +86,7 @@ enum {
 #define MQVS_F_TIMING 0x100u       /* per-launch HIP-event timing in mqvs_last_search_stats */
 
 typedef struct mqvs_segment *mqvs_segment_t;
+typedef struct mqvs_index *mqvs_index_t; /* an index over a resident segment (index path, below) */
 typedef void *mqvs_stream_t; /* a hipStream_t, or NULL for the caller thread's stream */
 
 /* ---- lifecycle ---------------------------------------------------------- */
@@ -324,8 +325,38 @@ int mqvs_comm_init_loopback(int32_t nranks, mqvs_comm_t *out);
 int mqvs_sharded_search(mqvs_comm_t comm, mqvs_segment_t shard, const float *queries, int32_t nq, int32_t k,
                         int32_t metric, const uint8_t *filter, const uint8_t *row_exists, int64_t *out_ids,
                         float *out_dist, uint32_t flags, mqvs_stream_t stream);
-/* Calls of this communicator that took the one-sync fast path, and how many
- * of those were re-run on the validated path. */
+/* The index search of a part sharded by row range: every rank calls it with
+ * ITS OWN index, built (mqvs_index_build) or loaded (mqvs_index_load) over
+ * its shard segment.  Each rank keeps its own lists; nothing is shared
+ * between the ranks' builds, so nprobe counts lists of the rank's index (a
+ * part of R ranks probes R * nprobe lists in all).  All ranks pass the same
+ * queries, k, params string and MQVS_F_FIRST_STAGE / MQVS_F_RERANK_ALL bits;
+ * filter / row_exists are the shard's bitmaps.  The protocol is
+ * mqvs_sharded_search's (header, one exchange of the lists, device merge,
+ * fast and validated path, every rank returns a failing rank's error); only
+ * the local step differs: mqvs_index_search_ex of the rank's index with its
+ * exact cosine chunk-ordinal base, taken from the exchanged chunk counts.
+ * Every rank gets the merge, bit-identical to mqvs_merge_shards (row-range
+ * order) over the ranks' mqvs_index_search_ex results: ids (a registered
+ * row-ids map applied by each rank to its own list), distance bits (the
+ * approximate ones with MQVS_F_FIRST_STAGE), -1 padding.  When every rank's
+ * search is exhaustive (nprobe = its nlist, num_reorder >= its candidates)
+ * that is mqvs_search over the whole part, bit for bit.
+ * Ranks that disagree on the kind of call (FLAT or index), params or the two
+ * flag bits fail everywhere with MQVS_ERR_BAD_ARGUMENTS; a binary index fails
+ * everywhere with MQVS_ERR_LOGICAL; an index on another device than the
+ * communicator fails alone with MQVS_ERR_BAD_ARGUMENTS.  A communicator
+ * serves FLAT and index calls in any order (a change of kind runs the
+ * validated path).  MQVS_F_ASYNC is ignored; mqvs_index_last_stats on a rank
+ * reports its local search.
+ * Not covered: mqvs_rerank takes no base, so a sharded TWO-STAGE cosine
+ * search (MQVS_F_FIRST_STAGE here, mqvs_rerank per shard) under filters that
+ * empty whole chunks stays the caller's problem. */
+int mqvs_sharded_index_search(mqvs_comm_t comm, mqvs_index_t idx, const float *queries, int32_t nq, int32_t k,
+                              const char *params, const uint8_t *filter, const uint8_t *row_exists,
+                              int64_t *out_ids, float *out_dist, uint32_t flags, mqvs_stream_t stream);
+/* Calls of this communicator (FLAT and index) that took the one-sync fast
+ * path, and how many of those were re-run on the validated path. */
 int mqvs_comm_stats(mqvs_comm_t comm, int64_t *fast_calls, int64_t *redo_calls);
 
 /* Fill a device buffer with generator rows [row0, row0+n) (for queries). */
@@ -393,7 +424,6 @@ int mqvs_generate_device(uint64_t seed, int32_t mode, int64_t row0, int64_t n, i
  * serve dpad <= 1216, 32-query tiles dpad <= 2496 and 16-query tiles
  * dpad <= 5056; a segment of more dimensions than that (5056 there) is
  * refused with MQVS_ERR_BAD_ARGUMENTS and a message naming the limit. */
-typedef struct mqvs_index *mqvs_index_t;
 int mqvs_index_build(mqvs_segment_t seg, const char *index_type, const char *params, mqvs_index_t *out);
 int mqvs_index_free(mqvs_index_t idx);
 typedef struct {
@@ -440,6 +470,16 @@ int mqvs_index_plane(mqvs_index_t idx, int32_t *format, size_t *plane_bytes);
 int mqvs_index_search(mqvs_index_t idx, const float *queries, int32_t nq, int32_t k, const char *params,
                       const uint8_t *filter, const uint8_t *row_exists, int64_t *out_ids, float *out_dist,
                       uint32_t flags, mqvs_stream_t stream);
+/* mqvs_index_search for the index of a row-range shard of a part, with the
+ * cosine chunk-ordinal base given (as mqvs_search_ex: the number of granule
+ * chunks before the shard's first row that the reference searches).  The
+ * exact re-rank takes each row's query variant by base + the chunk's ordinal
+ * within the shard.  chunk_ord_base < 0: row_offset / granule_rows, which is
+ * mqvs_index_search; above INT32_MAX: MQVS_ERR_BAD_ARGUMENTS.  Only cosine
+ * results depend on it, and a MQVS_F_FIRST_STAGE search ignores it. */
+int mqvs_index_search_ex(mqvs_index_t idx, const float *queries, int32_t nq, int32_t k, const char *params,
+                         const uint8_t *filter, const uint8_t *row_exists, int64_t chunk_ord_base,
+                         int64_t *out_ids, float *out_dist, uint32_t flags, mqvs_stream_t stream);
 /* Introspection of the coarse step (no reference counterpart: the MSTG
  * library's quantizer is not exposed through VectorIndex; these let a caller
  * or a test check the probes against its own exact top-nprobe):

@@ -475,6 +475,20 @@ public:
         });
     }
 
+    /// The index of a row-range shard of a part (mqvs_index_search_ex), as
+    /// PartScan::searchShard: chunk_ord_base = the number of granule chunks
+    /// before the shard's first row that the reference searches (< 0:
+    /// row_offset / granule).  It selects the exact re-rank's cosine query
+    /// variants; other metrics and first-stage searches ignore it.
+    void searchShard(const float * queries, int32_t nq, int32_t query_dim, int32_t k, const std::string & params,
+                     const uint8_t * filter, const uint8_t * row_exists, int64_t chunk_ord_base,
+                     bool first_stage_only, int64_t * ids, float * dist) const
+    {
+        part.checkDimension(query_dim);
+        check(mqvs_index_search_ex(idx->h, queries, nq, k, params.c_str(), filter, row_exists, chunk_ord_base, ids,
+                                   dist, first_stage_only ? MQVS_F_FIRST_STAGE : 0u, nullptr));
+    }
+
     /// computeTopDistanceSubset (VIWithDataPart.cpp:838-856): exact distances of
     /// the first stage's candidates (part rows, -1 = none), top_k per query.
     void computeTopDistanceSubset(const float * queries, int32_t nq, const int64_t * first_stage_ids,
@@ -729,6 +743,19 @@ public:
         check(mqvs_init(device));
         check(mqvs_comm_init(nranks, rank, id.data(), &comm));
     }
+    /// A loopback group (mqvs_comm_init_loopback): nranks virtual ranks of
+    /// this process on `device`, one ShardComm each, every rank's calls on a
+    /// thread of its own.  For tests and one-GPU rehearsal of a layout.
+    static std::vector<std::unique_ptr<ShardComm>> loopback(int32_t nranks, int device)
+    {
+        check(mqvs_init(device));
+        std::vector<mqvs_comm_t> hs(static_cast<size_t>(nranks > 0 ? nranks : 1), nullptr);
+        check(mqvs_comm_init_loopback(nranks, hs.data()));
+        std::vector<std::unique_ptr<ShardComm>> out;
+        for (int32_t r = 0; r < nranks; ++r)
+            out.emplace_back(new ShardComm(hs[static_cast<size_t>(r)]));
+        return out;
+    }
     ShardComm(const ShardComm &) = delete;
     ShardComm & operator=(const ShardComm &) = delete;
     ~ShardComm() { (void)mqvs_comm_free(comm); }
@@ -742,6 +769,20 @@ public:
                                   dist, 0, nullptr));
     }
 
+    /// Collective: every rank passes ITS OWN index, built or loaded over its
+    /// shard, and the same queries, k, params and first_stage_only; each rank
+    /// receives the merge of the ranks' index searches (nq*k), each made with
+    /// its exact cosine chunk-ordinal base.  nprobe counts lists of the
+    /// rank's own index.  == one search over the whole part when every rank's
+    /// search is exhaustive (mqvs_sharded_index_search).
+    void searchIndex(const GpuIndex & index, const float * queries, int32_t nq, int32_t k,
+                     const std::string & params, const uint8_t * filter, const uint8_t * row_exists,
+                     bool first_stage_only, int64_t * ids, float * dist) const
+    {
+        check(mqvs_sharded_index_search(comm, index.handle(), queries, nq, k, params.c_str(), filter, row_exists,
+                                        ids, dist, first_stage_only ? MQVS_F_FIRST_STAGE : 0u, nullptr));
+    }
+
     /// Searches that synchronised the host once (a repeat of the last call
     /// every rank completed), and how many of them re-ran on the validated path.
     std::pair<int64_t, int64_t> stats() const
@@ -752,6 +793,7 @@ public:
     }
 
 private:
+    explicit ShardComm(mqvs_comm_t h) : comm(h) {}
     mqvs_comm_t comm = nullptr;
 };
 

@@ -49,13 +49,15 @@ SYMBOLS = [
     "mqvs_search", "mqvs_search_ex", "mqvs_knn_raw", "mqvs_rerank", "mqvs_merge_shards", "mqvs_generate_device",
     "mqvs_last_search_stats", "mqvs_set_timing", "mqvs_set_batch_mode", "mqvs_set_gather_mode", "mqvs_set_prefilter",
     "mqvs_set_scratch_budget", "mqvs_measure_read_bandwidth", "mqvs_set_workspace_budget", "mqvs_workspace_stats",
-    "mqvs_index_build", "mqvs_index_free", "mqvs_index_info", "mqvs_index_search", "mqvs_index_last_stats",
+    "mqvs_index_build", "mqvs_index_free", "mqvs_index_info", "mqvs_index_search", "mqvs_index_search_ex",
+    "mqvs_index_last_stats",
     "mqvs_index_centroids", "mqvs_index_probes", "mqvs_index_plane",
     "mqvs_index_search_binary", "mqvs_index_centroids_binary", "mqvs_index_probes_binary",
     "mqvs_index_save_size", "mqvs_index_save", "mqvs_index_load", "mqvs_index_blob_info", "mqvs_index_lists",
     "mqvs_segment_create_binary", "mqvs_search_binary", "mqvs_knn_binary_raw",
     "mqvs_segment_create_from_column", "mqvs_async_check",
     "mqvs_comm_unique_id", "mqvs_comm_init", "mqvs_comm_init_loopback", "mqvs_comm_free", "mqvs_sharded_search", "mqvs_comm_stats",
+    "mqvs_sharded_index_search",
     "mqvs_index_set_row_ids_map", "mqvs_decoupled_filter",
     "mqvs_cache_create", "mqvs_cache_free", "mqvs_cache_put", "mqvs_cache_acquire", "mqvs_cache_release",
     "mqvs_cache_remove", "mqvs_cache_stats", "mqvs_inject_fault", "mqvs_set_wait_mode",
@@ -171,6 +173,7 @@ def _load(path=LIB_PATH):
         "mqvs_index_free": ([P], ctypes.c_int),
         "mqvs_index_info": ([P, P], ctypes.c_int),
         "mqvs_index_search": ([P, P, I32, I32, ctypes.c_char_p, P, P, P, P, U32, P], ctypes.c_int),
+        "mqvs_index_search_ex": ([P, P, I32, I32, ctypes.c_char_p, P, P, I64, P, P, U32, P], ctypes.c_int),
         "mqvs_index_last_stats": ([P], ctypes.c_int),
         "mqvs_index_centroids": ([P, P, I64], ctypes.c_int),
         "mqvs_index_probes": ([P, P, I32, ctypes.c_char_p, P], ctypes.c_int),
@@ -193,6 +196,7 @@ def _load(path=LIB_PATH):
         "mqvs_comm_init_loopback": ([I32, P], ctypes.c_int),
         "mqvs_comm_free": ([P], ctypes.c_int),
         "mqvs_sharded_search": ([P, P, P, I32, I32, I32, P, P, P, P, U32, P], ctypes.c_int),
+        "mqvs_sharded_index_search": ([P, P, P, I32, I32, ctypes.c_char_p, P, P, P, P, U32, P], ctypes.c_int),
         "mqvs_comm_stats": ([P, P, P], ctypes.c_int),
         "mqvs_index_set_row_ids_map": ([P, P, I64, U32], ctypes.c_int),
         "mqvs_decoupled_filter": ([P, I64, P, P, I64, U32, P, I64, U32, P], ctypes.c_int),

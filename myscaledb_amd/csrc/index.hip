@@ -936,16 +936,23 @@ int mqvs_index_plane(mqvs_index_t idx, int32_t *format, size_t *plane_bytes) {
     });
 }
 
-int mqvs_index_search(mqvs_index_t idx, const float *queries, int32_t nq, int32_t k, const char *params,
-                      const uint8_t *filter, const uint8_t *row_exists, int64_t *out_ids, float *out_dist,
-                      uint32_t flags, mqvs_stream_t stream) {
+int mqvs_index_search_ex(mqvs_index_t idx, const float *queries, int32_t nq, int32_t k, const char *params,
+                         const uint8_t *filter, const uint8_t *row_exists, int64_t chunk_ord_base, int64_t *out_ids,
+                         float *out_dist, uint32_t flags, mqvs_stream_t stream) {
     return guarded([&] {
         fault_point();
+        if (chunk_ord_base > INT32_MAX) fail(MQVS_ERR_BAD_ARGUMENTS, "chunk_ord_base out of range");
         WaitScope wsc{4, (uint64_t)(uintptr_t)idx, (uint64_t)nq, (uint64_t)k, wait_str_hash(params), filter != nullptr,
                       row_exists != nullptr, flags};
         search_index_impl(idx, queries, nq, k, params, filter, row_exists, out_ids, out_dist, flags,
-                          (hipStream_t)stream, 0);
+                          (hipStream_t)stream, 0, 0, chunk_ord_base);
     });
+}
+
+int mqvs_index_search(mqvs_index_t idx, const float *queries, int32_t nq, int32_t k, const char *params,
+                      const uint8_t *filter, const uint8_t *row_exists, int64_t *out_ids, float *out_dist,
+                      uint32_t flags, mqvs_stream_t stream) {
+    return mqvs_index_search_ex(idx, queries, nq, k, params, filter, row_exists, -1, out_ids, out_dist, flags, stream);
 }
 
 int mqvs_index_centroids(mqvs_index_t idx, float *out, int64_t cap) {

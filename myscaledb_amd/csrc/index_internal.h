@@ -88,6 +88,10 @@ struct IndexWorkspace final : WsExt {
     hipStream_t side = nullptr;
     int64_t *host = nullptr;  // pinned: the search's stats [4] and status word (one sync, no staging copies)
     CallIO io;  // staged inputs and outputs of host-pointer searches
+    // an ASYNC search with a flag word of the caller's left its stats in
+    // `host`: index_collect_stats reads them after the caller's sync
+    bool pending = false, pending_tev = false;
+    mqvs_index_search_stats pending_st{};
     GBuf qvars, qnorms, qmu, qlam, status, qhi, probes, cprobes, rows, ord, dmap, dwords, pdist, cqhi, gmax, crec, cbq,
         craw, ibq, qdelta, pstats, q8, q8exp, q8rec;
     ListBufs coarse, fine;
@@ -178,7 +182,11 @@ void finish_index(mqvs_index *ix, const int32_t *assign, bool from_blob, hipStre
 extern thread_local int64_t *t_probes_out;  // mqvs_index_probes
 void search_index_impl(mqvs_index *ix, const float *queries, int nq, int k, const char *params, const uint8_t *filter,
                        const uint8_t *exists, int64_t *out_ids, float *out_dist, uint32_t flags,
-                       hipStream_t user_stream, int formula_nq, int maxv_hint = 0);
+                       hipStream_t user_stream, int formula_nq, int maxv_hint = 0, int64_t ord_base = -1,
+                       int *async_word = nullptr);
+// the stats of this thread's last ASYNC search with a flag word of the
+// caller's (sharded.hip's fast path), after the caller's stream sync
+void index_collect_stats(int device);
 
 // ---- index_blob.hip
 size_t blob_bytes(const mqvs_index *ix);

@@ -246,6 +246,11 @@ struct IndexSearch {
     const uint32_t flags;
     const int fnq;         // the call's batch size, which selects the exact re-rank's distance formula
     const int nprobe, R;   // as resolved from the search parameters
+    // the ordinal of the segment's first searched chunk (cosine: selects the
+    // re-rank's query variant per row): the caller's (a row-range shard whose
+    // lower ranks' searched chunks were counted), else row_offset / granule
+    const int64_t ord_base;
+    int *const async_word;  // ASYNC: where the outcome flags go (null: the thread's sticky word)
     // ---- derived constants
     const int d;
     const bool dev, async, cos, first_stage, fp8;
@@ -297,13 +302,16 @@ struct IndexSearch {
 
     IndexSearch(mqvs_index *index, IndexWorkspace &w, hipStream_t stream, const float *q, int nq_, int k_,
                 const uint8_t *filter_, const uint8_t *exists_, int64_t *ids, float *dist, uint32_t flags_, int fnq_,
-                int nprobe_, int R_, int maxv_hint, const mqvs_index_search_stats &header)
+                int nprobe_, int R_, int maxv_hint, int64_t ord_base_, int *async_word_,
+                const mqvs_index_search_stats &header)
         : ix(index), seg(index->seg), ws(w), s(stream), queries(q), nq(nq_), k(k_), filter(filter_), exists(exists_),
-          out_ids(ids), out_dist(dist), flags(flags_), fnq(fnq_), nprobe(nprobe_), R(R_), d(seg->d),
+          out_ids(ids), out_dist(dist), flags(flags_), fnq(fnq_), nprobe(nprobe_), R(R_),
+          ord_base(ord_base_ >= 0 ? ord_base_ : index->seg->row_offset / index->seg->granule),
+          async_word(async_word_), d(seg->d),
           dev(flags_ & MQVS_F_DEVICE_PTRS), async(dev && (flags_ & MQVS_F_ASYNC)),
           cos(index->metric == MQVS_METRIC_COSINE), first_stage(flags_ & MQVS_F_FIRST_STAGE),
           fp8(index->plane_fmt == MQVS_INDEX_PLANE_FP8), tev(timing_on(flags_)), split(cos && !first_stage),
-          ords(seg->row_offset / seg->granule + (seg->n + seg->granule - 1) / seg->granule),
+          ords(ord_base + (seg->n + seg->granule - 1) / seg->granule),
           maxv(cos ? (maxv_hint > 0 ? maxv_hint : kMaxVariants) : 1), qstride(round_up(d, 32)),
           join_guard{stream, w.join}, st(header) {}
 
@@ -320,6 +328,7 @@ struct IndexSearch {
     void fork_chain();
     void fine();
     void rerank();
+    void queue_stats();
     void finish_async();
     int finish_sync();
 
@@ -488,6 +497,12 @@ bool IndexSearch::coarse_pick() {
 
 void IndexSearch::coarse_flat() {
     float *pd = (float *)ws.pdist.get(sizeof(float) * (size_t)nq * nprobe);
+    if (async && async_word) {
+        // (the nested search's candidate overflow is the caller's to see too)
+        search_segment_async(ix->cent, dq, nq, nprobe, ix->coarse_metric, nullptr, nullptr, probes, pd, 0, s, -1,
+                             async_word);
+        return;
+    }
     search_internal(ix->cent, dq, nq, nprobe, ix->coarse_metric, nullptr, nullptr, probes, pd,
                     MQVS_F_DEVICE_PTRS | (flags & MQVS_F_ASYNC), s);
 }
@@ -624,7 +639,7 @@ void IndexSearch::rerank() {
         MQVS_HIP(hipGetLastError());
         rp.chunk_ord = o;
     }
-    rp.ord_base = (int)(seg->row_offset / seg->granule);
+    rp.ord_base = (int)ord_base;
     rp.exists = dexists;
     rp.filter = nullptr;  // the scan applied the filter; candidates pass it
     rp.nonempty = seg->nonempty_bits;
@@ -641,26 +656,10 @@ void IndexSearch::rerank() {
     MQVS_HIP(hipGetLastError());
 }
 
-void IndexSearch::finish_async() {
-    const bool variants_matter = !first_stage && ords > maxv;
-    launch_async_flags(nullptr, status, variants_matter ? 1 : 0, async_sticky(seg->device, s), s);
-    MQVS_HIP(hipGetLastError());
-}
-
-int IndexSearch::finish_sync() {
-    int64_t *hs = ws.host;
-    int *hst = reinterpret_cast<int *>(ws.host + 4);
-    if (!dev) {
-        // (host outputs: copied before the final wait)
-        if (ix->row_ids_map) launch_map_ids(out.ids, (int64_t)nq * k, ix->row_ids_map, s);
-        ws.io.finish_begin(out, s);
-    }
-    int64_t *dstats = fine_stats.words;
-    launch_words_to_host(dstats, 4, status, 8, hs, hst, s, fine_stats.per_query ? dstats : nullptr, nq);
-    MQVS_HIP(hipGetLastError());
-    host_wait(s);
-    if (const int want = first_stage ? 0 : check_variant_chain(*hst, ords, maxv)) return want;
-    ws.io.finish_end(out);
+// the thread's stats from the pinned words of its last search (after the
+// wait that covers them)
+static void index_read_stats(IndexWorkspace &ws, mqvs_index_search_stats st, bool tev) {
+    const int64_t *hs = ws.host;
     st.values = hs[0];
     st.items = hs[1];
     st.plane_bytes = hs[2];
@@ -679,7 +678,55 @@ int IndexSearch::finish_sync() {
     st.rerank_ms = t[4];
     st.total_ms = tot;
     g_istats = st;
+}
+
+// the fine pass's stats and the status words -> the workspace's pinned words
+void IndexSearch::queue_stats() {
+    int64_t *dstats = fine_stats.words;
+    launch_words_to_host(dstats, 4, status, 8, ws.host, reinterpret_cast<int *>(ws.host + 4), s,
+                         fine_stats.per_query ? dstats : nullptr, nq);
+    MQVS_HIP(hipGetLastError());
+}
+
+void IndexSearch::finish_async() {
+    const bool variants_matter = !first_stage && ords > maxv;
+    launch_async_flags(nullptr, status, variants_matter ? 1 : 0, async_word ? async_word : async_sticky(seg->device, s),
+                       s);
+    MQVS_HIP(hipGetLastError());
+    if (async_word) {
+        // the stats land in pinned memory, read after the caller's sync
+        // (index_collect_stats)
+        queue_stats();
+        ws.pending = true;
+        ws.pending_tev = tev;
+        ws.pending_st = st;
+    }
+}
+
+int IndexSearch::finish_sync() {
+    int *hst = reinterpret_cast<int *>(ws.host + 4);
+    if (!dev) {
+        // (host outputs: copied before the final wait)
+        if (ix->row_ids_map) launch_map_ids(out.ids, (int64_t)nq * k, ix->row_ids_map, s);
+        ws.io.finish_begin(out, s);
+    }
+    queue_stats();
+    host_wait(s);
+    if (const int want = first_stage ? 0 : check_variant_chain(*hst, ords, maxv)) return want;
+    ws.io.finish_end(out);
+    ws.pending = false;
+    index_read_stats(ws, st, tev);
     return 0;
+}
+
+// the stats of this thread's last ASYNC search with a flag word of the
+// caller's on `device`, once the caller has synchronised its stream
+void index_collect_stats(int device) {
+    DeviceGuard guard(device);
+    IndexWorkspace &ws = index_workspace(device);
+    if (!ws.pending) return;
+    ws.pending = false;
+    index_read_stats(ws, ws.pending_st, ws.pending_tev);
 }
 
 // The driver: resolves the search parameters, splits into query sub-batches
@@ -688,9 +735,12 @@ int IndexSearch::finish_sync() {
 // them again with the larger one.
 // formula_nq: the call's batch size, which selects the exact re-rank's
 // distance formula (0: nq; query sub-batches keep the call's, see search.hip)
+// ord_base: the cosine chunk-ordinal base of a row-range shard (< 0:
+// row_offset / granule); the sub-batches and the re-run keep it.  async_word:
+// an ASYNC search's outcome flags go there instead of the sticky word.
 void search_index_impl(mqvs_index *ix, const float *queries, int nq, int k, const char *params, const uint8_t *filter,
                        const uint8_t *exists, int64_t *out_ids, float *out_dist, uint32_t flags,
-                       hipStream_t user_stream, int formula_nq, int maxv_hint) {
+                       hipStream_t user_stream, int formula_nq, int maxv_hint, int64_t ord_base, int *async_word) {
     const int fnq = formula_nq > 0 ? formula_nq : nq;
     check_search_args(ix, "index", ix && ix->binary ? "binary index: search it with mqvs_index_search_binary" : nullptr,
                       nq, k, queries, out_ids, out_dist);
@@ -722,7 +772,8 @@ void search_index_impl(mqvs_index *ix, const float *queries, int nq, int k, cons
             const int d = ix->seg->d;
             for_query_batches(nq, qb, [&](int q0, int m) {
                 search_index_impl(ix, queries + (size_t)q0 * d, m, k, params, filter, exists,
-                                  out_ids + (size_t)q0 * k, out_dist + (size_t)q0 * k, flags, user_stream, fnq);
+                                  out_ids + (size_t)q0 * k, out_dist + (size_t)q0 * k, flags, user_stream, fnq, 0,
+                                  ord_base, async_word);
             });
             g_istats.nq = nq;
             return;
@@ -739,9 +790,10 @@ void search_index_impl(mqvs_index *ix, const float *queries, int nq, int k, cons
     scope.set_stream(s);
     // (declared after the scope: its join guard runs before the scope is released)
     IndexSearch search(ix, ws, s, queries, nq, k, filter, exists, out_ids, out_dist, flags, fnq, nprobe, R, maxv_hint,
-                       st);
+                       ord_base, async_word, st);
     if (const int want = search.run())
-        search_index_impl(ix, queries, nq, k, params, filter, exists, out_ids, out_dist, flags, user_stream, fnq, want);
+        search_index_impl(ix, queries, nq, k, params, filter, exists, out_ids, out_dist, flags, user_stream, fnq, want,
+                          ord_base, async_word);
 }
 
 }  // namespace mqvs

@@ -1,5 +1,6 @@
 // sharded.hip -- one data part sharded by row range over the GPUs of a node:
-// mqvs_comm_* (an RCCL communicator, one rank per GPU) and mqvs_sharded_search.
+// mqvs_comm_* (an RCCL communicator, one rank per GPU), mqvs_sharded_search
+// and mqvs_sharded_index_search.
 //
 // The reference runs one scan per data part and merges the parts' top-k on
 // the host (MergeTreeBaseSearchManager.cpp:207-297; across servers, the
@@ -20,9 +21,16 @@
 //   4. the device merge by (distance, rank, position) = the unsharded order.
 // Every rank ends with the merged result, bit-identical to a single-GPU
 // search of the whole part.
+// mqvs_sharded_index_search is the same protocol with another step 2: every
+// rank searches the index it built (or loaded) over its own shard
+// (search_index_impl with the base of step 1, which its exact re-rank takes
+// the cosine query variants by).  The result is the merge of the ranks' index
+// searches; it is the whole part's exact result when every rank's search is
+// exhaustive.  The two calls differ in local_search and in the call key only.
 //
 // Host round trips.  A call equal to the last call all ranks validated
-// together (same shard, nq, k, metric, bitmaps present) takes the FAST path:
+// together (same shard, nq, k, metric, bitmaps present; an index call: same
+// index, params and flags) takes the FAST path:
 // 1-4 are enqueued back to back (the local search without its own sync, the
 // cosine base taken from the last validated call) and the host synchronises
 // ONCE, to read the exchanged table -- every rank reads the same table and so
@@ -48,6 +56,7 @@
 #include <string>
 #include <vector>
 
+#include "index_internal.h"
 #include "mqvs_internal.h"
 
 namespace mqvs {
@@ -154,13 +163,15 @@ struct LoopGroup {
 struct ShardCall {
     bool valid = false;
     const void *shard = nullptr;
+    const void *index = nullptr;  // an index call: the rank's index (null: FLAT)
+    int64_t key = 0;              // an index call: call_key of its params and flags
     int64_t row_offset = 0, rows = 0, nq = 0, k = 0, metric = 0, d = 0;
     bool filter = false, exists = false, dev = false;
     int64_t ord_base = -1;  // cosine, no PREWHERE filter: the verified chunk-ordinal base
     bool same(const ShardCall &o) const {
-        return valid && o.shard == shard && o.row_offset == row_offset && o.rows == rows && o.nq == nq &&
-               o.k == k && o.metric == metric && o.d == d && o.filter == filter && o.exists == exists &&
-               o.dev == dev;
+        return valid && o.shard == shard && o.index == index && o.key == key && o.row_offset == row_offset &&
+               o.rows == rows && o.nq == nq && o.k == k && o.metric == metric && o.d == d && o.filter == filter &&
+               o.exists == exists && o.dev == dev;
     }
 };
 
@@ -225,7 +236,8 @@ void comm_group_end(mqvs_comm *c) {
 // rank's view of the call and its outcome.  kHdrFast: the rank took the fast
 // path; kHdrOrd: the cosine chunk-ordinal base it searched with; kHdrFlags:
 // its local search's fallback flags (an int in the low half); kHdrNk: nq * k;
-// kHdrCode: the status code of a failed rank.
+// kHdrCode: the status code of a failed rank; kHdrKind: 0 a FLAT call, 1 an
+// index call; kHdrKey: an index call's params string and flag bits (call_key).
 enum {
     kHdrOffset,
     kHdrRows,
@@ -239,6 +251,8 @@ enum {
     kHdrFlags,
     kHdrNk,
     kHdrCode,
+    kHdrKind,
+    kHdrKey,
     kHdrWords = 16
 };
 
@@ -350,10 +364,39 @@ int mqvs_comm_free(mqvs_comm_t c) {
 
 namespace {
 
+struct CallArgs {
+    mqvs_segment *shard;
+    mqvs_index *index;   // an index call: the rank's index over `shard` (null: FLAT)
+    const char *params;  // and its search parameters
+    int64_t key;         // call_key(params, flags); 0 for FLAT
+    const float *queries;
+    int nq, k, metric;
+    const uint8_t *filter, *exists;
+    int64_t *out_ids;
+    float *out_dist;
+    uint32_t search_flags;  // per-call path flags for the local search
+    bool dev;
+    hipStream_t s;
+    size_t nk;
+    bool cos;  // cosine over more than one rank: chunk-ordinal bases exchanged
+};
+
+// What the ranks of an index call must agree on beside nq, k and metric: the
+// params string as given and the two flags that change the result
+int64_t call_key(const char *params, uint32_t flags) {
+    uint64_t h = wait_str_hash(params);
+    h = (h ^ (uint64_t)(flags & (MQVS_F_FIRST_STAGE | MQVS_F_RERANK_ALL))) * 1099511628211ull;
+    return (int64_t)(h >> 1);
+}
+
 // this rank's header words (the outcome fields ok / code / flags as given)
-void fill_header(int64_t *h, const mqvs_segment *shard, int nq, int k, int metric, bool fast, int64_t ord,
-                 int64_t nk, int code) {
+void fill_header(int64_t *h, const CallArgs &a, bool fast, int64_t ord, int code) {
+    const mqvs_segment *shard = a.shard;
+    const int nq = a.nq, k = a.k, metric = a.metric;
+    const int64_t nk = (int64_t)a.nk;
     for (int i = 0; i < kHdrWords; ++i) h[i] = 0;
+    h[kHdrKind] = a.index ? 1 : 0;
+    h[kHdrKey] = a.key;
     h[kHdrOffset] = shard->row_offset;
     h[kHdrRows] = shard->n;
     h[kHdrGranule] = shard->granule;
@@ -371,7 +414,8 @@ const int64_t *row(const int64_t *table, int r) { return table + (size_t)kHdrWor
 // The checks every rank makes on the same exchanged table (so every rank
 // decides the same way): a failed rank fails the call everywhere with its
 // code; shards must follow each other in row order on granule boundaries and
-// the ranks must agree on granule, dimension, nq, k and metric.
+// the ranks must agree on granule, dimension, nq, k and metric, on the kind
+// of the call (FLAT or index) and on an index call's params and flags.
 void check_table(const mqvs_comm *c, const int64_t *t, int local_code, const std::string &local_err) {
     for (int r = 0; r < c->nranks; ++r)
         if (!row(t, r)[kHdrOk])
@@ -385,6 +429,9 @@ void check_table(const mqvs_comm *c, const int64_t *t, int local_code, const std
                                              " ends at " + std::to_string(a[kHdrOffset] + a[kHdrRows]));
         if (b[kHdrGranule] != a[kHdrGranule] || b[kHdrDim] != a[kHdrDim] || b[kHdrCall] != a[kHdrCall])
             fail(MQVS_ERR_BAD_ARGUMENTS, "ranks disagree on granule, dimension, nq, k or metric");
+        if (b[kHdrKind] != a[kHdrKind] || b[kHdrKey] != a[kHdrKey])
+            fail(MQVS_ERR_BAD_ARGUMENTS, "ranks disagree on the kind of search (FLAT or index), the index search "
+                                         "params or the first-stage / re-rank-all flags");
     }
     if (c->nranks > 1 && t[kHdrGranule] > 0)
         for (int r = 0; r + 1 < c->nranks; ++r)
@@ -392,27 +439,17 @@ void check_table(const mqvs_comm *c, const int64_t *t, int local_code, const std
                 fail(MQVS_ERR_BAD_ARGUMENTS, "shard boundaries must be granule aligned");
 }
 
-struct CallArgs {
-    mqvs_segment *shard;
-    const float *queries;
-    int nq, k, metric;
-    const uint8_t *filter, *exists;
-    int64_t *out_ids;
-    float *out_dist;
-    uint32_t search_flags;  // per-call path flags for the local search
-    bool dev;
-    hipStream_t s;
-    size_t nk;
-    bool cos;  // cosine over more than one rank: chunk-ordinal bases exchanged
-};
-
 // Inputs on the device (host pointers: copied into the communicator's
 // buffers) and the argument checks of mqvs_search.
 void stage_inputs(mqvs_comm *c, const CallArgs &a, const float *&dq, const uint8_t *&dfilter,
                   const uint8_t *&dexists) {
     mqvs_segment *shard = a.shard;
-    check_search_args(shard, "segment", shard->binary ? "binary segments are not sharded" : nullptr, a.nq, a.k,
-                      a.queries, a.out_ids, a.out_dist);
+    if (a.index)
+        check_search_args(a.index, "index", a.index->binary ? "binary indexes are not sharded" : nullptr, a.nq, a.k,
+                          a.queries, a.out_ids, a.out_dist);
+    else
+        check_search_args(shard, "segment", shard->binary ? "binary segments are not sharded" : nullptr, a.nq, a.k,
+                          a.queries, a.out_ids, a.out_dist);
     dq = a.queries;
     dfilter = a.filter;
     dexists = a.exists;
@@ -476,6 +513,32 @@ void merge_out(mqvs_comm *c, const CallArgs &a, const Bufs &b) {
     }
 }
 
+// The one step FLAT and index calls differ in: this rank's top-k of its shard
+// into the local lists, with device pointers on the call's stream.
+// flag_word null: synchronous, with the search's host-driven fallbacks (the
+// validated path).  Else nothing waits: the fallback flags (bit 0 candidate
+// overflow, bit 1 cosine variant table too short -- the index's host-driven
+// re-run with a larger table) are OR-ed into *flag_word, and
+// local_collect_stats fills the thread's stats after the caller's sync.
+void local_search(const CallArgs &a, const float *dq, const uint8_t *dfilter, const uint8_t *dexists, const Bufs &b,
+                  int64_t ord_base, int *flag_word) {
+    if (a.index)
+        search_index_impl(a.index, dq, a.nq, a.k, a.params, dfilter, dexists, b.li, b.ld,
+                          a.search_flags | MQVS_F_DEVICE_PTRS | (flag_word ? MQVS_F_ASYNC : 0), a.s, 0, 0, ord_base,
+                          flag_word);
+    else if (flag_word)
+        search_segment_async(a.shard, dq, a.nq, a.k, a.metric, dfilter, dexists, b.li, b.ld, a.search_flags, a.s,
+                             ord_base, flag_word);
+    else
+        search_segment(a.shard, dq, a.nq, a.k, a.metric, dfilter, dexists, b.li, b.ld, a.search_flags, a.s, ord_base);
+}
+void local_collect_stats(const mqvs_comm *c, const CallArgs &a) {
+    if (a.index)
+        index_collect_stats(c->device);
+    else
+        search_collect_stats(c->device);
+}
+
 enum class Fast { kDone, kRedo };
 
 // The fast path: this rank's call equals the call every rank validated last
@@ -496,7 +559,7 @@ Fast fast_search(mqvs_comm *c, const CallArgs &a) {
                                                               : shard->row_offset / shard->granule;
     std::string local_err;
     int local_code = MQVS_OK;
-    fill_header(hm, shard, a.nq, a.k, a.metric, true, ord, (int64_t)a.nk, MQVS_OK);
+    fill_header(hm, a, true, ord, MQVS_OK);
     MQVS_HIP(hipMemcpyAsync(mine, hm, sizeof(int64_t) * kHdrWords, hipMemcpyHostToDevice, a.s));
     Bufs b;
     try {
@@ -508,14 +571,13 @@ Fast fast_search(mqvs_comm *c, const CallArgs &a) {
             launch_count_active_chunks(dfilter, shard->nonempty_bits, dexists, shard->n, shard->granule,
                                        b.chunk_flags, mine + kHdrChunks, a.s);
         if (a.nk)
-            search_segment_async(shard, dq, a.nq, a.k, a.metric, dfilter, dexists, b.li, b.ld, a.search_flags, a.s,
-                                 ord, (int *)(mine + kHdrFlags));
+            local_search(a, dq, dfilter, dexists, b, ord, (int *)(mine + kHdrFlags));
     } catch (const Error &e) {
         local_err = e.msg;
         local_code = e.code;
         // (this rank still joins the exchange, with its failure in the header;
         // the staging buffer is rewritten whole, so the copy above is harmless)
-        fill_header(hm, shard, a.nq, a.k, a.metric, true, ord, (int64_t)a.nk, e.code);
+        fill_header(hm, a, true, ord, e.code);
         MQVS_HIP(hipMemcpyAsync(mine, hm, sizeof(int64_t) * kHdrWords, hipMemcpyHostToDevice, a.s));
     }
     const bool have = local_code == MQVS_OK;
@@ -537,7 +599,7 @@ Fast fast_search(mqvs_comm *c, const CallArgs &a) {
     if (have) merge_out(c, a, b);
     MQVS_HIP(hipMemcpyAsync(ht, hd, sizeof(int64_t) * kHdrWords * c->nranks, hipMemcpyDeviceToHost, a.s));
     host_wait(a.s);
-    if (have && a.nk) search_collect_stats(c->device);
+    if (have && a.nk) local_collect_stats(c, a);
     try {
         for (int r = 0; r < c->nranks; ++r)
             if (!row(ht, r)[kHdrFast])
@@ -586,7 +648,7 @@ void slow_search(mqvs_comm *c, const CallArgs &a, const ShardCall &call) {
         local_code = e.code;
     }
     // 1. header exchange
-    fill_header(hm, shard, a.nq, a.k, a.metric, false, -1, (int64_t)a.nk, local_code);
+    fill_header(hm, a, false, -1, local_code);
     MQVS_HIP(hipMemcpyAsync(mine, hm, sizeof(int64_t) * kHdrWords, hipMemcpyHostToDevice, a.s));
     if (a.cos && local_code == MQVS_OK)
         launch_count_active_chunks(dfilter, shard->nonempty_bits, dexists, shard->n, shard->granule, b.chunk_flags,
@@ -623,15 +685,14 @@ void slow_search(mqvs_comm *c, const CallArgs &a, const ShardCall &call) {
     if (a.nk) {
         // 2. local top-k (ids part-global: the shard's row_offset applied)
         try {
-            search_segment(shard, dq, a.nq, a.k, a.metric, dfilter, dexists, b.li, b.ld, a.search_flags, a.s,
-                           ord_base);
+            local_search(a, dq, dfilter, dexists, b, ord_base, nullptr);
         } catch (const Error &e) {
             local_err = e.msg;
             local_code = e.code;
         }
         // 3. one exchange: (ids, distances) of every rank, rank-major, and
         // each rank's status (in the header table)
-        fill_header(hm, shard, a.nq, a.k, a.metric, false, ord_base, (int64_t)a.nk, local_code);
+        fill_header(hm, a, false, ord_base, local_code);
         MQVS_HIP(hipMemcpyAsync(mine, hm, sizeof(int64_t) * kHdrWords, hipMemcpyHostToDevice, a.s));
         comm_group_start(c);
         comm_all_gather(c, b.li, b.ai, sizeof(int64_t) * a.nk, a.s);
@@ -652,6 +713,33 @@ void slow_search(mqvs_comm *c, const CallArgs &a, const ShardCall &call) {
     c->last.ord_base = a.cos && !a.filter ? ord_base : -1;
 }
 
+// the protocol of one call, under the communicator's lock: the fast path
+// when the call repeats the last validated one, else (or when the fast path
+// asks for it) the validated path
+void sharded_call(mqvs_comm *c, const CallArgs &a) {
+    ShardCall call;
+    call.valid = true;
+    call.shard = a.shard;
+    call.index = a.index;
+    call.key = a.key;
+    call.row_offset = a.shard->row_offset;
+    call.rows = a.shard->n;
+    call.nq = a.nq;
+    call.k = a.k;
+    call.metric = a.metric;
+    call.d = a.shard->d;
+    call.filter = a.filter != nullptr;
+    call.exists = a.exists != nullptr;
+    call.dev = a.dev;
+    if (c->last.same(call)) {
+        c->fast_calls++;
+        if (fast_search(c, a) == Fast::kDone) return;
+        // every rank read the same table and re-runs together
+        c->redo_calls++;
+    }
+    slow_search(c, a, call);
+}
+
 }  // namespace
 
 extern "C" {
@@ -667,30 +755,34 @@ int mqvs_sharded_search(mqvs_comm_t c, mqvs_segment_t shard, const float *querie
         DeviceGuard guard(c->device);
         WaitScope wsc{6, (uint64_t)(uintptr_t)c, (uint64_t)(uintptr_t)shard, (uint64_t)nq, (uint64_t)k,
                       (uint64_t)metric, filter != nullptr, row_exists != nullptr, flags};
-        CallArgs a{shard, queries, nq, k, metric, filter, row_exists, out_ids, out_dist,
+        CallArgs a{shard, nullptr, nullptr, 0, queries, nq, k, metric, filter, row_exists, out_ids, out_dist,
                    flags & ~(MQVS_F_ASYNC | MQVS_F_DEVICE_PTRS), (flags & MQVS_F_DEVICE_PTRS) != 0,
                    stream ? (hipStream_t)stream : c->stream,
                    (size_t)std::max(nq, 0) * (size_t)std::max(k, 0),
                    metric == MQVS_METRIC_COSINE && c->nranks > 1};
-        ShardCall call;
-        call.valid = true;
-        call.shard = shard;
-        call.row_offset = shard->row_offset;
-        call.rows = shard->n;
-        call.nq = nq;
-        call.k = k;
-        call.metric = metric;
-        call.d = shard->d;
-        call.filter = filter != nullptr;
-        call.exists = row_exists != nullptr;
-        call.dev = a.dev;
-        if (c->last.same(call)) {
-            c->fast_calls++;
-            if (fast_search(c, a) == Fast::kDone) return;
-            // every rank read the same table and re-runs together
-            c->redo_calls++;
-        }
-        slow_search(c, a, call);
+        sharded_call(c, a);
+    });
+}
+
+int mqvs_sharded_index_search(mqvs_comm_t c, mqvs_index_t idx, const float *queries, int32_t nq, int32_t k,
+                              const char *params, const uint8_t *filter, const uint8_t *row_exists, int64_t *out_ids,
+                              float *out_dist, uint32_t flags, mqvs_stream_t stream) {
+    return guarded([&] {
+        // (a call that cannot take part in the exchange fails alone)
+        if (!c || !idx || !idx->seg) fail(MQVS_ERR_BAD_ARGUMENTS, "null communicator or index");
+        mqvs_segment *shard = idx->seg;
+        if (shard->device != c->device) fail(MQVS_ERR_BAD_ARGUMENTS, "index and communicator on different devices");
+        std::lock_guard<std::mutex> lock(c->mu);
+        DeviceGuard guard(c->device);
+        WaitScope wsc{8, (uint64_t)(uintptr_t)c, (uint64_t)(uintptr_t)idx, (uint64_t)nq, (uint64_t)k,
+                      wait_str_hash(params), filter != nullptr, row_exists != nullptr, flags};
+        // (a first-stage search ignores the chunk-ordinal base: no count, no exchange of it)
+        CallArgs a{shard, idx, params, call_key(params, flags), queries, nq, k, idx->metric, filter, row_exists,
+                   out_ids, out_dist, flags & ~(MQVS_F_ASYNC | MQVS_F_DEVICE_PTRS),
+                   (flags & MQVS_F_DEVICE_PTRS) != 0, stream ? (hipStream_t)stream : c->stream,
+                   (size_t)std::max(nq, 0) * (size_t)std::max(k, 0),
+                   idx->metric == MQVS_METRIC_COSINE && c->nranks > 1 && !(flags & MQVS_F_FIRST_STAGE)};
+        sharded_call(c, a);
     });
 }
 

@@ -144,7 +144,8 @@ class ShardedScan:
 class RcclComm:
     """libmqvs's own RCCL communicator (mqvs_comm_*): one rank per GPU, the
     exchange of mqvs_sharded_search.  unique_id() runs on one rank; its 128
-    bytes reach the others out of band (here: a torch.distributed broadcast)."""
+    bytes reach the others out of band (here: a torch.distributed broadcast).
+    sharded_index_search is the same exchange around each rank's own index."""
 
     def __init__(self, nranks: int, rank: int, uid: bytes):
         import ctypes
@@ -220,6 +221,54 @@ class RcclComm:
         self._lib.check(self._lib.lib.mqvs_sharded_search(
             self._h, segment._h, _ptr(q), nq, k, m, _ptr(_host_u8(filter_bitmap)), _ptr(_host_u8(row_exists)),
             _ptr(ids), _ptr(dist), 0, stream))
+        return ids, dist
+
+    def sharded_index_search(self, index, queries, k, params=None, filter_bitmap=None, row_exists=None,
+                             first_stage_only=False, out=None, stream=None, rerank_all=False):
+        """mqvs_sharded_index_search: this rank's `index` (a VectorIndex built
+        or loaded over its shard segment) searched with `params`, the per-rank
+        top-k exchanged and merged as in sharded_search; every rank returns
+        the merged [nq, k] result.  Every rank passes the same queries, k,
+        params and first_stage_only / rerank_all; bitmaps are the shard's own.
+        nprobe counts lists of the rank's own index."""
+        from .vector_index import _params
+        from .vector_scan import _host_f32, _host_u8, _is_torch, _ptr
+        from ._lib import F_DEVICE_PTRS, F_FIRST_STAGE, F_RERANK_ALL
+        fs = (F_FIRST_STAGE if first_stage_only else 0) | (F_RERANK_ALL if rerank_all else 0)
+        pr = _params(params)
+        if _is_torch(queries):
+            import torch
+            assert queries.is_cuda and queries.is_contiguous() and queries.dtype == torch.float32, \
+                "queries: a contiguous float32 CUDA tensor"
+            for b in (filter_bitmap, row_exists):
+                assert b is None or (b.is_cuda and b.is_contiguous() and b.dtype == torch.uint8), \
+                    "bitmaps: contiguous uint8 CUDA tensors"
+            nq = queries.shape[0]
+            if out is None:
+                ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
+                dist = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
+            else:
+                ids, dist = out
+                assert ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int64
+                assert dist.is_cuda and dist.is_contiguous() and dist.dtype == torch.float32
+            if stream is None:
+                stream = torch.cuda.current_stream(queries.device).cuda_stream
+            self._lib.check(self._lib.lib.mqvs_sharded_index_search(
+                self._h, index._h, _ptr(queries), nq, k, pr, _ptr(filter_bitmap), _ptr(row_exists), _ptr(ids),
+                _ptr(dist), F_DEVICE_PTRS | fs, stream))
+            return ids, dist
+        q = _host_f32(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        nq = q.shape[0]
+        if out is None:
+            ids = np.empty((nq, k), np.int64)
+            dist = np.empty((nq, k), np.float32)
+        else:
+            ids, dist = out
+        self._lib.check(self._lib.lib.mqvs_sharded_index_search(
+            self._h, index._h, _ptr(q), nq, k, pr, _ptr(_host_u8(filter_bitmap)), _ptr(_host_u8(row_exists)),
+            _ptr(ids), _ptr(dist), fs, stream))
         return ids, dist
 
     def stats(self):

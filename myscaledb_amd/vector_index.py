@@ -97,14 +97,19 @@ class VectorIndex:
         return buf.reshape(-1)[: nq * npb].reshape(nq, npb).copy()
 
     def search(self, queries, k, params=None, filter_bitmap=None, row_exists=None, first_stage_only=False,
-               out=None, async_=False, stream=None, rerank_all=False):
+               out=None, async_=False, stream=None, rerank_all=False, chunk_ord_base=None):
         """(ids[nq,k] int64, dist[nq,k] float32), reference order, -1 padded.
         first_stage_only: the k best rows by the approximate distance (stage 1
         of a two-stage search; re-rank with compute_top_distance_subset).
         rerank_all: re-rank every num_reorder candidate (MQVS_F_RERANK_ALL; the
-        default bound pruning gives the same results)."""
+        default bound pruning gives the same results).
+        chunk_ord_base: the index of a row-range shard: how many granule chunks
+        before its first row the reference searches (mqvs_index_search_ex;
+        sharded.chunk_ordinal_base).  None: row_offset / granule.  Only cosine
+        results depend on it."""
         fs = (F_FIRST_STAGE if first_stage_only else 0) | (F_RERANK_ALL if rerank_all else 0)
         pr = _params(params)
+        base = -1 if chunk_ord_base is None else int(chunk_ord_base)
         if _is_torch(queries):
             import torch
             assert queries.is_cuda and queries.is_contiguous() and queries.dtype == torch.float32
@@ -115,8 +120,9 @@ class VectorIndex:
             else:
                 ids, dist = out
             flags = F_DEVICE_PTRS | (F_ASYNC if async_ else 0) | fs
-            check(lib.mqvs_index_search(self._h, _ptr(queries), nq, k, pr, _ptr(filter_bitmap), _ptr(row_exists),
-                                        _ptr(ids), _ptr(dist), flags, ctypes.c_void_p(stream) if stream else None))
+            check(lib.mqvs_index_search_ex(self._h, _ptr(queries), nq, k, pr, _ptr(filter_bitmap), _ptr(row_exists),
+                                           base, _ptr(ids), _ptr(dist), flags,
+                                           ctypes.c_void_p(stream) if stream else None))
             return ids, dist
         q = _host_f32(queries)
         if q.ndim == 1:
@@ -126,8 +132,8 @@ class VectorIndex:
             raise _lib.MqvsError(_lib.ERR_LOGICAL, "The dimension of searched index and input doesn't match.")
         ids = np.empty((nq, k), np.int64)
         dist = np.empty((nq, k), np.float32)
-        check(lib.mqvs_index_search(self._h, _ptr(q), nq, k, pr, _ptr(_host_u8(filter_bitmap)),
-                                    _ptr(_host_u8(row_exists)), _ptr(ids), _ptr(dist), fs, None))
+        check(lib.mqvs_index_search_ex(self._h, _ptr(q), nq, k, pr, _ptr(_host_u8(filter_bitmap)),
+                                       _ptr(_host_u8(row_exists)), base, _ptr(ids), _ptr(dist), fs, None))
         return ids, dist
 
     def save(self) -> bytes:
