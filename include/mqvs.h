@@ -226,6 +226,97 @@ int mqvs_merge_shards(int32_t nshards, int32_t nq, int32_t k, int32_t metric,
                       const int64_t *in_ids, const float *in_dist, int64_t *out_ids,
                       float *out_dist, uint32_t flags, mqvs_stream_t stream);
 
+/* ---- part groups: many small resident parts searched in one fused call
+ * The parts of a MergeTree table that have no index yet (fresh inserts, recent
+ * merges) are many and small; the reference scans them with one thread per
+ * part (MergeTreeSelectWithHybridSearchProcessor.cpp:1212-1241) and merges the
+ * per-part top-k in getTotalTopSearchResultImpl
+ * (MergeTreeBaseSearchManager.cpp:207-297).  A group is an ordered list of
+ * Float32 segments -- the list order is the part order of that merge, the
+ * reference's insertion order -- and mqvs_part_group_search returns, for every
+ * input, exactly what
+ *     mqvs_search(segs[p], queries, nq, k, metric, filters[p], row_exists[p])
+ *         for every p (the same nq, so the same faiss formula branch), then
+ *     mqvs_merge_shards(nparts, ..., MQVS_F_PART_MERGE) over the lists in
+ *         group order
+ * returns: ids, distance bits, order and padding (id -1, FLT_MAX, or FLT_MIN
+ * for IP) match bit for bit.  out_part[q][i] is the position in the group of
+ * the part result i came from (-1 in padding slots): the caller reads the
+ * winning rows from that part.
+ *
+ * The group borrows the segments (they outlive it; the cache and the caller
+ * keep ownership).  Creation is cheap: it validates and remembers the handles,
+ * copies no rows and makes no pass over them, so a caller may build a group
+ * per query as its set of parts changes.  The per-part descriptors (rows
+ * pointer, n, granule, row offset, chunk ordinals and non-empty bitmap, tile
+ * and column prefix sums, the call's bitmaps) are taken from the live segments
+ * by every search and uploaded as one small table with it: a segment may move
+ * its rows between HBM and host memory (mqvs_segment_set_rows_host) while a
+ * group holds it, and the group itself holds no device memory (hbm_bytes 0).
+ * Errors of mqvs_part_group_create: nparts < 1, a null handle, or segments on
+ * different devices -> MQVS_ERR_BAD_ARGUMENTS; a binary segment, differing
+ * dimensions, or cosine and non-cosine segments mixed -> MQVS_ERR_LOGICAL.
+ * mqvs_part_group_info: rows = the sum of the parts' rows; fusable_parts = the
+ * parts whose rows are in HBM and number at most the part-group row limit.
+ *
+ * mqvs_part_group_search.  filters / row_exists: host arrays of nparts
+ * pointers; either array may be NULL, any entry may be NULL; each bitmap
+ * (LSB-first) covers its own part's rows.  With MQVS_F_DEVICE_PTRS the
+ * queries, the three outputs and every bitmap are device pointers (the two
+ * pointer arrays stay host arrays).  MQVS_F_ASYNC is ignored: the call always
+ * ends with the merged result, after one host wait (as the sharded calls).
+ * nparts * k > 2^20 -> MQVS_ERR_BAD_ARGUMENTS (the merge's limit); a metric
+ * the segments were not prepared for -> MQVS_ERR_LOGICAL.  The call honours
+ * mqvs_inject_fault as mqvs_search does (outputs untouched) and its scratch
+ * passes the workspace budget gate, counted in the thread's workspace.
+ * Two routes, the same bits on both:
+ *   fused     nq < 20, k <= 4096, and the part has its rows in HBM and at most
+ *             the part-group row limit of them: all such parts are searched by
+ *             one query prep, one grouped exact fp32 scan (dense values), one
+ *             grouped select and the merge -- a launch chain whose length
+ *             does not depend on nparts (a group whose dense [nq][rows] matrix
+ *             passes mqvs_set_scratch_budget runs scan + select per slice of
+ *             parts).  Every row of a part is a candidate of its select, so no
+ *             candidate list can overflow and no part is ever re-run (redo
+ *             stays 0).  Cosine: the query variant table is sized for the part
+ *             with the most chunk ordinals (up to 16384, within the scratch
+ *             budget), so a chain that does not repeat needs no second run.
+ *   per part  every other part and call (nq >= 20, k > 4096, rows in host
+ *             memory, larger parts; also a cosine part that carries a PREWHERE
+ *             filter, whose chunk ordinals come from the filter, and a cosine
+ *             part of more chunk ordinals than the variant table may hold):
+ *             mqvs_search's own path on the same stream; the list joins the
+ *             same merge.
+ * mqvs_set_part_group_rows: the row limit of the fused route (default 131072,
+ * the largest measured part size at which the fused route still beat the
+ * per-part one at nq 1 and nq 16, profiles/part_group; at most 2^24); returns
+ * the previous value, 0 leaves it unchanged. */
+typedef struct mqvs_part_group *mqvs_part_group_t;
+int mqvs_part_group_create(const mqvs_segment_t *segs, int32_t nparts, mqvs_part_group_t *out);
+int mqvs_part_group_free(mqvs_part_group_t group);
+int mqvs_part_group_info(mqvs_part_group_t group, int32_t *nparts, int64_t *rows, int32_t *d,
+                         int32_t *fusable_parts, size_t *hbm_bytes);
+int mqvs_part_group_search(mqvs_part_group_t group, const float *queries, int32_t nq, int32_t k, int32_t metric,
+                           const uint8_t *const *filters, const uint8_t *const *row_exists,
+                           int32_t *out_part, int64_t *out_ids, float *out_dist,
+                           uint32_t flags, mqvs_stream_t stream);
+/* Stats of the calling thread's last mqvs_part_group_search. */
+typedef struct {
+    double total_ms;      /* host time of the call (only with mqvs_set_timing(1) or MQVS_F_TIMING) */
+    int64_t fused_rows;   /* rows of the fused parts */
+    int32_t parts;
+    int32_t fused_parts;
+    int32_t looped_parts; /* parts searched by the per-part route */
+    int32_t launches;     /* kernel launches the call queued for the fused route and the merge
+                             (the per-part searches' own launches are not counted) */
+    int32_t redo;         /* fused parts re-run per part (always 0: see above) */
+    int32_t nq;
+    int32_t k;
+    int32_t reserved;
+} mqvs_part_group_stats;
+int mqvs_part_group_last_stats(mqvs_part_group_stats *out);
+int64_t mqvs_set_part_group_rows(int64_t rows);
+
 /* ---- column ingest: a part's Array(Float32) column from its compressed files
  * Replaces the per-granule host read + copy of vectorScanWithoutIndex
  * (MergeTreeVSManager.cpp:1348-1393): data_bin = the bytes of the nested

@@ -892,4 +892,100 @@ inline void mergePartResults(int32_t nparts, int32_t nq, int32_t k, int mqvs_met
                             nullptr));
 }
 
+/// The rows getTotalTopSearchResultImpl hands on for one call: per query the
+/// best k over all parts, query-major, best first, padding slots dropped.
+struct PartRows
+{
+    std::vector<uint32_t> part;       /// position of the part in the group
+    std::vector<uint32_t> label;      /// row id in that part
+    std::vector<uint32_t> vector_id;  /// query index
+    std::vector<float> distance;
+};
+
+/// The parts of a table that have no index yet, searched in one fused call
+/// (mqvs_part_group_search): the per-part PartScan::search calls and
+/// mergePartResults in one launch chain and one host wait.  The group borrows
+/// the PartScans' segments, which must outlive it; the list order is the
+/// part order of the merge (the reference's insertion order).
+class PartGroup
+{
+public:
+    explicit PartGroup(const std::vector<const PartScan *> & parts)
+    {
+        std::vector<mqvs_segment_t> segs;
+        for (const PartScan * p : parts)
+            segs.push_back(p ? p->handle() : nullptr);
+        mqvs_part_group_t g = nullptr;
+        check(mqvs_part_group_create(segs.data(), static_cast<int32_t>(segs.size()), &g));
+        group = std::make_shared<GroupHandle>(g, true);
+        nparts = static_cast<int32_t>(segs.size());
+        metric = parts[0]->metricId();
+        dim = parts[0]->dimension();
+    }
+
+    int32_t parts() const { return nparts; }
+    mqvs_part_group_t handle() const { return group->h; }
+
+    /// The CPU path the call replaces: the part scans and the cross-part merge,
+    /// same arguments and outputs.
+    using GroupFallback = std::function<void(const float * queries, int32_t nq, int32_t k,
+                                             const uint8_t * const * filters, const uint8_t * const * row_exists,
+                                             int32_t * part, int64_t * ids, float * dist)>;
+
+    /// Raw merged top-k: part / ids / dist nq*k (caller-owned); padding slots
+    /// hold part -1, id -1, FLT_MAX (FLT_MIN for IP).  filters / row_exists:
+    /// nparts bitmap pointers (either array, and any entry, may be nullptr).
+    /// fallback: runs instead when the device fails (isFallbackStatus).
+    void search(const float * queries, int32_t nq, int32_t k, const uint8_t * const * filters,
+                const uint8_t * const * row_exists, int32_t * part, int64_t * ids, float * dist, uint32_t flags = 0,
+                const GroupFallback & fallback = nullptr) const
+    {
+        const int st = mqvs_part_group_search(group->h, queries, nq, k, metric, filters, row_exists, part, ids, dist,
+                                              flags, nullptr);
+        checkOrFallback(st, static_cast<bool>(fallback),
+                        [&] { fallback(queries, nq, k, filters, row_exists, part, ids, dist); });
+    }
+
+    /// The labelled rows of the merged result, after the reference's dimension check.
+    PartRows search(const float * queries, int32_t nq, int32_t query_dim, int32_t k,
+                    const uint8_t * const * filters = nullptr, const uint8_t * const * row_exists = nullptr,
+                    const GroupFallback & fallback = nullptr) const
+    {
+        if (query_dim != dim)
+            throw DB::Exception(DB::ErrorCodes::LOGICAL_ERROR, "{}",
+                                "The dimension of searched vector (" + std::to_string(query_dim)
+                                    + ") doesn't match the dimension of the vector column (" + std::to_string(dim) + ")");
+        std::vector<int32_t> part(static_cast<size_t>(nq) * k);
+        std::vector<int64_t> ids(part.size());
+        std::vector<float> dist(part.size());
+        search(queries, nq, k, filters, row_exists, part.data(), ids.data(), dist.data(), 0, fallback);
+        PartRows out;
+        for (size_t i = 0; i < ids.size(); ++i)
+        {
+            if (ids[i] <= -1)
+                continue;
+            out.part.push_back(static_cast<uint32_t>(part[i]));
+            out.label.push_back(static_cast<uint32_t>(ids[i]));
+            out.vector_id.push_back(static_cast<uint32_t>(i / static_cast<size_t>(k)));
+            out.distance.push_back(dist[i]);
+        }
+        return out;
+    }
+
+    /// The calling thread's last search (mqvs_part_group_last_stats).
+    static mqvs_part_group_stats lastStats()
+    {
+        mqvs_part_group_stats st{};
+        check(mqvs_part_group_last_stats(&st));
+        return st;
+    }
+
+private:
+    using GroupHandle = Handle<mqvs_part_group_t, mqvs_part_group_free>;
+    std::shared_ptr<GroupHandle> group;
+    int32_t nparts = 0;
+    int32_t dim = 0;
+    int metric = 0;
+};
+
 }

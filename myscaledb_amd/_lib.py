@@ -61,6 +61,8 @@ SYMBOLS = [
     "mqvs_index_set_row_ids_map", "mqvs_decoupled_filter",
     "mqvs_cache_create", "mqvs_cache_free", "mqvs_cache_put", "mqvs_cache_acquire", "mqvs_cache_release",
     "mqvs_cache_remove", "mqvs_cache_stats", "mqvs_inject_fault", "mqvs_set_wait_mode",
+    "mqvs_part_group_create", "mqvs_part_group_free", "mqvs_part_group_info", "mqvs_part_group_search",
+    "mqvs_part_group_last_stats", "mqvs_set_part_group_rows",
 ]
 
 
@@ -76,6 +78,14 @@ class SearchStats(ctypes.Structure):
                 ("prefilter", ctypes.c_int32), ("batch_kernel", ctypes.c_int32),
                 ("survivors_total", ctypes.c_int64), ("survivors_max", ctypes.c_int32),
                 ("candidates_max", ctypes.c_int32)]
+
+
+class PartGroupStats(ctypes.Structure):
+    _fields_ = [("total_ms", ctypes.c_double), ("fused_rows", ctypes.c_int64),
+                ("parts", ctypes.c_int32), ("fused_parts", ctypes.c_int32),
+                ("looped_parts", ctypes.c_int32), ("launches", ctypes.c_int32),
+                ("redo", ctypes.c_int32), ("nq", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
 
 
 class IndexInfo(ctypes.Structure):
@@ -207,6 +217,12 @@ def _load(path=LIB_PATH):
         "mqvs_cache_release": ([P, ctypes.c_char_p, P], ctypes.c_int),
         "mqvs_cache_remove": ([P, ctypes.c_char_p], ctypes.c_int),
         "mqvs_cache_stats": ([P, P], ctypes.c_int),
+        "mqvs_part_group_create": ([P, I32, P], ctypes.c_int),
+        "mqvs_part_group_free": ([P], ctypes.c_int),
+        "mqvs_part_group_info": ([P, P, P, P, P, P], ctypes.c_int),
+        "mqvs_part_group_search": ([P, P, I32, I32, I32, P, P, P, P, P, U32, P], ctypes.c_int),
+        "mqvs_part_group_last_stats": ([P], ctypes.c_int),
+        "mqvs_set_part_group_rows": ([I64], I64),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

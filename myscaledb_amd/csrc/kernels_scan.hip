@@ -87,10 +87,13 @@ __device__ inline void emit(const ScanParams &p, int j, int64_t pos, int64_t row
 constexpr int SB_K = 32;            // floats per stage
 constexpr int SB_LD = SB_K + 4;     // padded LDS row (16-B aligned, conflict-free b128)
 
+// One tile of the scan (the whole workgroup calls it with the same ti): the
+// body k_scan_small and the part-group kernel k_scan_group share, so both
+// compute a row's value with the same instructions.  tile / qtile: the
+// workgroup's LDS stages, free on entry and on return.
 template <int NQ, int METRIC, bool PROBE, bool VEC4>
-__global__ __launch_bounds__(256) void k_scan_small(ScanParams p) {
-    __shared__ __attribute__((aligned(16))) float tile[2][kSmallRows * SB_LD];
-    __shared__ __attribute__((aligned(16))) float qtile[2][NQ * SB_K];
+__device__ __forceinline__ void scan_small_tile(const ScanParams &p, int64_t ti, float (*tile)[kSmallRows * SB_LD],
+                                                float (*qtile)[NQ * SB_K]) {
     const int t = threadIdx.x;
     const int d = p.d;
     const int nst = (d + SB_K - 1) / SB_K;
@@ -98,10 +101,10 @@ __global__ __launch_bounds__(256) void k_scan_small(ScanParams p) {
     // threads t < NQ*8 stage one float4 of the query slice per stage
     const int qj = t >> 3, qc = (t & 7) * 4;
     const bool qload = qj < NQ && qj < p.nq;
-    for (int64_t ti = blockIdx.x; ti < p.tiles; ti += gridDim.x) {
+    {
         int64_t r0, r1, chunk;
         tile_range(p, ti, r0, r1, chunk);
-        if (r0 >= r1) continue;  // tile past the end of a partial last granule (block-uniform)
+        if (r0 >= r1) return;  // tile past the end of a partial last granule (block-uniform)
         const int ord = chunk_ordinal(p, chunk);
         const int64_t pos = r0 + t;
         const bool inrange = pos < r1;
@@ -110,7 +113,7 @@ __global__ __launch_bounds__(256) void k_scan_small(ScanParams p) {
         if (ord < 0) {  // chunk never searched by the reference (all arrays empty)
             if (PROBE && inrange)
                 for (int j = 0; j < p.nq; ++j) emit<METRIC, true>(p, j, pos, row, false, 0.f);
-            continue;
+            return;
         }
         const float *qsrc = qload
             ? p.qvars + ((int64_t)qj * p.maxv + variant_of(p, qj, ord)) * qstride + qc
@@ -193,6 +196,13 @@ __global__ __launch_bounds__(256) void k_scan_small(ScanParams p) {
     }
 }
 
+template <int NQ, int METRIC, bool PROBE, bool VEC4>
+__global__ __launch_bounds__(256) void k_scan_small(ScanParams p) {
+    __shared__ __attribute__((aligned(16))) float tile[2][kSmallRows * SB_LD];
+    __shared__ __attribute__((aligned(16))) float qtile[2][NQ * SB_K];
+    for (int64_t ti = blockIdx.x; ti < p.tiles; ti += gridDim.x) scan_small_tile<NQ, METRIC, PROBE, VEC4>(p, ti, tile, qtile);
+}
+
 template <int NQ, int METRIC, bool PROBE>
 static void launch_small_t(const ScanParams &p, hipStream_t s) {
     int64_t grid = p.tiles < 4096 ? p.tiles : 4096;
@@ -232,6 +242,76 @@ void launch_scan_small(const ScanParams &p, int metric, bool probe, hipStream_t 
         default:
             probe ? launch_small_m<kMetricIpRaw, true>(p, s) : launch_small_m<kMetricIpRaw, false>(p, s);
             break;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Part-group scan (part_group.hip): k_scan_small's PROBE tiles over many small
+// parts in one launch.  Tile ti of the launch belongs to the slot whose
+// [tile0, next tile0) holds it (slots[nslots] is the sentinel); the workgroup
+// takes that part's fields into its ScanParams and runs the shared tile body,
+// so a row's value is the one mqvs_search computes for it.
+template <int NQ, int METRIC, bool VEC4>
+__global__ __launch_bounds__(256) void k_scan_group(ScanParams p, const GroupSlot *slots, int nslots, int64_t tiles) {
+    __shared__ __attribute__((aligned(16))) float tile[2][kSmallRows * SB_LD];
+    __shared__ __attribute__((aligned(16))) float qtile[2][NQ * SB_K];
+    float *const matrix = p.probe;
+    for (int64_t ti = blockIdx.x; ti < tiles; ti += gridDim.x) {
+        // the last slot with tile0 <= ti (slots without tiles are skipped)
+        int lo = 0, hi = nslots;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (slots[mid].tile0 <= ti) lo = mid;
+            else hi = mid;
+        }
+        const GroupSlot &g = slots[lo];
+        p.rows = g.rows;
+        p.n = g.n;
+        p.chunk_rows = g.granule;
+        p.chunk_ord = g.chunk_ord;
+        p.ord_base = (int)(g.row_offset / g.granule);
+        p.filter = g.filter;
+        p.exists = g.exists;
+        p.nonempty = g.nonempty;
+        p.row_begin = 0;
+        p.row_end = g.n;
+        p.tiles_per_chunk = g.tiles_per_chunk;
+        p.tile_rows = kSmallRows;
+        p.probe = matrix + g.col0;
+        scan_small_tile<NQ, METRIC, true, VEC4>(p, ti - g.tile0, tile, qtile);
+    }
+}
+
+template <int NQ, int METRIC>
+static void launch_group_t(const ScanParams &p, const GroupSlot *slots, int nslots, int64_t tiles, hipStream_t s) {
+    const int64_t grid = tiles < 4096 ? tiles : 4096;
+    if (grid < 1) return;
+    if (p.d % 4 == 0)
+        hipLaunchKernelGGL((k_scan_group<NQ, METRIC, true>), dim3((unsigned)grid), dim3(256), 0, s, p, slots, nslots,
+                           tiles);
+    else
+        hipLaunchKernelGGL((k_scan_group<NQ, METRIC, false>), dim3((unsigned)grid), dim3(256), 0, s, p, slots, nslots,
+                           tiles);
+}
+
+template <int METRIC>
+static void launch_group_m(const ScanParams &p, const GroupSlot *slots, int nslots, int64_t tiles, hipStream_t s) {
+    const int nq = p.nq;
+    if (nq <= 1) launch_group_t<1, METRIC>(p, slots, nslots, tiles, s);
+    else if (nq <= 2) launch_group_t<2, METRIC>(p, slots, nslots, tiles, s);
+    else if (nq <= 4) launch_group_t<4, METRIC>(p, slots, nslots, tiles, s);
+    else if (nq <= 8) launch_group_t<8, METRIC>(p, slots, nslots, tiles, s);
+    else if (nq <= 12) launch_group_t<12, METRIC>(p, slots, nslots, tiles, s);
+    else if (nq <= 16) launch_group_t<16, METRIC>(p, slots, nslots, tiles, s);
+    else launch_group_t<20, METRIC>(p, slots, nslots, tiles, s);
+}
+
+void launch_scan_group(const ScanParams &base, const GroupSlot *slots, int nslots, int64_t tiles, int metric,
+                       hipStream_t s) {
+    switch (metric) {
+        case MQVS_METRIC_L2: launch_group_m<MQVS_METRIC_L2>(base, slots, nslots, tiles, s); break;
+        case MQVS_METRIC_IP: launch_group_m<MQVS_METRIC_IP>(base, slots, nslots, tiles, s); break;
+        default: launch_group_m<MQVS_METRIC_COSINE>(base, slots, nslots, tiles, s); break;
     }
 }
 

@@ -65,28 +65,19 @@ __global__ __launch_bounds__(SEL_THREADS) void k_cand_tau(const Cand *cand, cons
 }
 
 
-// scratch (k > kSortCap): 2 kLargeCap records per query in global memory;
-// the records to sort then may exceed the LDS sort (global_sort).
-template <int METRIC>
-__global__ __launch_bounds__(SEL_THREADS) void k_final_select(const Cand *cand,
-                                                             const int *cand_count, int cap,
-                                                             int k, int64_t chunk_rows,
-                                                             int64_t id_offset, int64_t *out_ids,
-                                                             float *out_dist, int *overflow,
-                                                             uint4 *scratch) {
-    extern __shared__ __attribute__((aligned(16))) uint4 recs[];  // kSortCap records
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t sh[4];
-    __shared__ int s_cnt;
-    const int q = blockIdx.x;
-    uint4 *g = scratch ? scratch + (int64_t)q * 2 * kLargeCap : nullptr;
+// The select of one query's n candidates c[0, n) (the whole workgroup calls
+// it): the body k_final_select and the part-group select share, so the tie
+// order is stated once.  c[i] yields candidate i as a Cand (a list, or a view
+// of a dense row of values).  out_ids / out_dist: the query's k outputs; g:
+// its 2 kLargeCap records of global scratch, or null; recs: kSortCap records
+// of LDS; hist[256], sh[4], s_cnt_p: LDS words.
+template <int METRIC, typename CandAt>
+__device__ __forceinline__ void final_select_body(const CandAt c, const int n, int k, int64_t chunk_rows,
+                                                  int64_t id_offset, int64_t *out_ids, float *out_dist,
+                                                  int *overflow, uint4 *g, uint4 *recs, uint32_t *hist,
+                                                  uint32_t *sh, int *s_cnt_p) {
+    int &s_cnt = *s_cnt_p;
     const int lcap = g ? kLargeCap : kSortCap;  // records this call can sort
-    int n = cand_count[q];
-    if (n > cap) {
-        if (threadIdx.x == 0) atomicOr(overflow, 1);
-        n = cap;
-    }
-    const Cand *c = cand + (int64_t)q * cap;
     auto make_rec = [&](const Cand &e) {
         uint4 r;
         r.x = key32<METRIC>(e.raw);
@@ -213,8 +204,8 @@ __global__ __launch_bounds__(SEL_THREADS) void k_final_select(const Cand *cand,
                 id = (int64_t)sorted[i].w + id_offset;
                 dist = key_to_value(METRIC, sorted[i].x);
             }
-            out_ids[(int64_t)q * k + i] = id;
-            out_dist[(int64_t)q * k + i] = dist;
+            out_ids[i] = id;
+            out_dist[i] = dist;
         }
         return;
     }
@@ -231,9 +222,64 @@ __global__ __launch_bounds__(SEL_THREADS) void k_final_select(const Cand *cand,
             id = (int64_t)recs[i].w + id_offset;
             dist = key_to_value(METRIC, recs[i].x);
         }
-        out_ids[(int64_t)q * k + i] = id;
-        out_dist[(int64_t)q * k + i] = dist;
+        out_ids[i] = id;
+        out_dist[i] = dist;
     }
+}
+
+// scratch (k > kSortCap): 2 kLargeCap records per query in global memory;
+// the records to sort then may exceed the LDS sort (global_sort).
+template <int METRIC>
+__global__ __launch_bounds__(SEL_THREADS) void k_final_select(const Cand *cand,
+                                                             const int *cand_count, int cap,
+                                                             int k, int64_t chunk_rows,
+                                                             int64_t id_offset, int64_t *out_ids,
+                                                             float *out_dist, int *overflow,
+                                                             uint4 *scratch) {
+    extern __shared__ __attribute__((aligned(16))) uint4 recs[];  // kSortCap records
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t sh[4];
+    __shared__ int s_cnt;
+    const int q = blockIdx.x;
+    uint4 *g = scratch ? scratch + (int64_t)q * 2 * kLargeCap : nullptr;
+    int n = cand_count[q];
+    if (n > cap) {
+        if (threadIdx.x == 0) atomicOr(overflow, 1);
+        n = cap;
+    }
+    final_select_body<METRIC>(cand + (int64_t)q * cap, n, k, chunk_rows, id_offset, out_ids + (int64_t)q * k,
+                              out_dist + (int64_t)q * k, overflow, g, recs, hist, sh, &s_cnt);
+}
+
+// Part-group select (part_group.hip): workgroup (slot, query) runs the final
+// select over the slot's slice of the dense matrix -- every row of the part is
+// a candidate (NaN = invalid row: its key is the never-returned one), so no
+// list can overflow and ties at the k-th key are cut by the same rules.
+struct DenseCand {
+    const float *v;
+    __device__ Cand operator[](int64_t i) const {
+        Cand c;
+        c.raw = v[i];
+        c.row = (uint32_t)i;
+        return c;
+    }
+};
+
+template <int METRIC>
+__global__ __launch_bounds__(SEL_THREADS) void k_select_group(const float *matrix, int64_t ld,
+                                                             const GroupSlot *slots, int nq, int k,
+                                                             int64_t *list_ids, float *list_dist,
+                                                             int *overflow) {
+    extern __shared__ __attribute__((aligned(16))) uint4 recs[];  // kSortCap records
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t sh[4];
+    __shared__ int s_cnt;
+    const int q = blockIdx.x % nq;
+    const GroupSlot &g = slots[blockIdx.x / nq];
+    const DenseCand c{matrix + (int64_t)q * ld + g.col0};
+    const int64_t o = ((int64_t)g.part * nq + q) * k;
+    final_select_body<METRIC>(c, (int)g.n, k, g.granule, g.row_offset, list_ids + o, list_dist + o, overflow,
+                              (uint4 *)nullptr, recs, hist, sh, &s_cnt);
 }
 
 // Merge of per-list results: key (distance, list, position).  rev_ties (IP
@@ -247,7 +293,8 @@ __global__ __launch_bounds__(SEL_THREADS) void k_merge_shards(int nshards, int n
                                                              const int64_t *in_ids,
                                                              const float *in_dist,
                                                              int64_t *out_ids, float *out_dist,
-                                                             int rev_ties, uint4 *scratch) {
+                                                             int rev_ties, uint4 *scratch,
+                                                             int32_t *out_list) {
     extern __shared__ __attribute__((aligned(16))) uint4 recs[];
     const int q = blockIdx.x;
     const int n = nshards * k;
@@ -266,7 +313,46 @@ __global__ __launch_bounds__(SEL_THREADS) void k_merge_shards(int nshards, int n
     };
     const uint4 *sorted = recs;
     int N = 1;
+    // More records than the LDS sort holds (many lists): the k best are among
+    // the records whose distance key is at or under the k-th distance key, so
+    // when those fit (no mass tie at the cut) only they are sorted, in LDS --
+    // the same first k records in the same order as the sort of all n.
+    int m = n;
     if (n > kSortCap) {
+        __shared__ uint32_t hist[256];
+        __shared__ uint32_t sh[4];
+        __shared__ int s_cnt;
+        auto keyof = [&](int64_t i) { return record((int)i).x; };
+        const uint32_t th = block_radix_select(keyof, n, k, hist, sh);  // 0xFFFFFFFE: fewer than k records
+        if (threadIdx.x == 0) s_cnt = 0;
+        __syncthreads();
+        int mine = 0;
+        for (int i = threadIdx.x; i < n; i += SEL_THREADS) {
+            const uint32_t x = keyof(i);
+            mine += x != 0xFFFFFFFFu && x <= th;
+        }
+        if (mine) atomicAdd(&s_cnt, mine);
+        __syncthreads();
+        m = s_cnt;
+        __syncthreads();
+        if (m <= kSortCap) {
+            if (threadIdx.x == 0) s_cnt = 0;
+            __syncthreads();
+            for (int i = threadIdx.x; i < n; i += SEL_THREADS) {
+                const uint4 r = record(i);
+                if (r.x != 0xFFFFFFFFu && r.x <= th) recs[atomicAdd(&s_cnt, 1)] = r;
+            }
+            while (N < m) N <<= 1;
+            __syncthreads();
+            for (int i = m + threadIdx.x; i < N; i += SEL_THREADS)
+                recs[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+            __syncthreads();
+            block_bitonic_sort(recs, N);
+        }
+    }
+    if (n > kSortCap && m <= kSortCap) {
+        // (sorted above)
+    } else if (n > kSortCap) {
         uint4 *g = scratch + (int64_t)q * 2 * n;
         for (int i = threadIdx.x; i < n; i += SEL_THREADS) g[i] = record(i);
         __syncthreads();
@@ -283,15 +369,18 @@ __global__ __launch_bounds__(SEL_THREADS) void k_merge_shards(int nshards, int n
     for (int i = threadIdx.x; i < k; i += SEL_THREADS) {
         int64_t id = -1;
         float dist = pad;
+        int32_t list = -1;
         if (i < N && sorted[i].x != 0xFFFFFFFFu) {
             const int src = (int)sorted[i].w;
             const int s = src / k, pos = src % k;
             const int64_t off = ((int64_t)s * nq + q) * k + pos;
             id = in_ids[off];
             dist = in_dist[off];
+            list = s;
         }
         out_ids[(int64_t)q * k + i] = id;
         out_dist[(int64_t)q * k + i] = dist;
+        if (out_list) out_list[(int64_t)q * k + i] = list;
     }
 }
 
@@ -356,19 +445,34 @@ void launch_final_select(const Cand *cand, const int *cand_count, int cand_cap, 
 
 template <int M>
 static void merge_shards_t(int nshards, int nq, int k, const int64_t *in_ids, const float *in_dist,
-                           int64_t *out_ids, float *out_dist, int rev_ties, uint4 *scratch, hipStream_t s) {
+                           int64_t *out_ids, float *out_dist, int rev_ties, uint4 *scratch, int32_t *out_list,
+                           hipStream_t s) {
     hipLaunchKernelGGL(k_merge_shards<M>, dim3(nq), dim3(SEL_THREADS),
                        sort_lds(nshards * k > kSortCap ? kSortCap : nshards * k), s, nshards, nq, k, in_ids, in_dist,
-                       out_ids, out_dist, rev_ties, scratch);
+                       out_ids, out_dist, rev_ties, scratch, out_list);
 }
 
 void launch_merge_shards(int nshards, int nq, int k, int metric, const int64_t *in_ids,
                          const float *in_dist, int64_t *out_ids, float *out_dist, bool part_merge,
-                         uint4 *scratch, hipStream_t s) {
+                         uint4 *scratch, hipStream_t s, int32_t *out_list) {
     if (nq <= 0) return;
     const int rev = part_merge && (metric == MQVS_METRIC_IP || metric == kMetricIpRaw);
     MQVS_DISPATCH_METRIC(metric, merge_shards_t,
-                         (nshards, nq, k, in_ids, in_dist, out_ids, out_dist, rev, scratch, s));
+                         (nshards, nq, k, in_ids, in_dist, out_ids, out_dist, rev, scratch, out_list, s));
+}
+
+template <int M>
+static void select_group_t(const float *matrix, int64_t ld, const GroupSlot *slots, int nslots, int nq, int k,
+                           int64_t *list_ids, float *list_dist, int *overflow, hipStream_t s) {
+    hipLaunchKernelGGL(k_select_group<M>, dim3((unsigned)nslots * nq), dim3(SEL_THREADS), sort_lds(kSortCap), s,
+                       matrix, ld, slots, nq, k, list_ids, list_dist, overflow);
+}
+
+void launch_select_group(const float *matrix, int64_t ld, const GroupSlot *slots, int nslots, int nq, int k,
+                         int metric, int64_t *list_ids, float *list_dist, int *overflow, hipStream_t s) {
+    if (nq <= 0 || nslots <= 0) return;
+    MQVS_DISPATCH_METRIC(metric, select_group_t,
+                         (matrix, ld, slots, nslots, nq, k, list_ids, list_dist, overflow, s));
 }
 
 // ---------------------------------------------------------------------------

@@ -248,6 +248,33 @@ __device__ inline bool row_valid(const ScanParams &p, int64_t r) {
 }
 
 // ---------------------------------------------------------------------------
+// Part groups (part_group.hip): one slot per part of a grouped launch.  The
+// grouped scan maps workgroup tiles [tile0, next slot's tile0) to the part and
+// writes its dense values into columns [col0, col0 + n) of the launch's
+// [nq][ld] matrix; the grouped select reads each (slot, query) slice.  A
+// table of m slots ends with a sentinel whose tile0 is the launch's tile count.
+struct GroupSlot {
+    const float *rows;
+    const int *chunk_ord;     // as ScanParams::chunk_ord
+    const uint8_t *nonempty;
+    const uint8_t *filter;    // this call's PREWHERE bitmap of the part, or null
+    const uint8_t *exists;    // this call's lightweight-delete bitmap, or null
+    int64_t n, granule, row_offset;
+    int64_t tile0, col0;
+    int64_t tiles_per_chunk;  // chunk-aligned tiling of the part (0 = contiguous)
+    int32_t part;             // position in the group (the merge's list index)
+    int32_t pad;
+};
+// base: d, nq, qvars, qmu, qlam, maxv, blas_nq, probe (the matrix), probe_ld
+// set; the per-part fields come from the slots
+void launch_scan_group(const ScanParams &base, const GroupSlot *slots, int nslots, int64_t tiles, int metric,
+                       hipStream_t s);
+// per (slot, query) the k best rows of the slice in mqvs_search's order ->
+// list_ids / list_dist [group parts][nq][k] at the slot's part
+void launch_select_group(const float *matrix, int64_t ld, const GroupSlot *slots, int nslots, int nq, int k,
+                         int metric, int64_t *list_ids, float *list_dist, int *overflow, hipStream_t s);
+
+// ---------------------------------------------------------------------------
 // Launchers (kernels_*.hip)
 void launch_scan_small(const ScanParams &p, int metric, bool probe, hipStream_t s);
 void launch_gather_count(const uint8_t *filter, const uint8_t *nonempty, const uint8_t *exists, int64_t n,
@@ -315,9 +342,10 @@ void launch_final_select(const Cand *cand, const int *cand_count, int cand_cap, 
                          int metric, int64_t chunk_rows, int64_t id_offset, int64_t *out_ids,
                          float *out_dist, int *overflow, uint4 *scratch, hipStream_t s);
 // scratch: 2 nshards k uint4 records per query when nshards k > kSortCap
+// out_list (optional): [nq][k] the list each result came from, -1 in padding
 void launch_merge_shards(int nshards, int nq, int k, int metric, const int64_t *in_ids,
                          const float *in_dist, int64_t *out_ids, float *out_dist, bool part_merge,
-                         uint4 *scratch, hipStream_t s);
+                         uint4 *scratch, hipStream_t s, int32_t *out_list = nullptr);
 void launch_normalize_rows(float *rows, int64_t n, int d, hipStream_t s);
 void launch_row_norms(const float *rows, int64_t n, int d, float *norms, hipStream_t s);
 // maxv: variants stored per query (1 unless cosine)

@@ -1,0 +1,358 @@
+// part_group.hip -- many small resident parts searched in one fused call
+// (mqvs_part_group_*, include/mqvs.h).
+//
+// The fused route is the FLAT search's exact small-batch path with a batch
+// dimension over parts:
+//   1. query prep        once per call (the cosine variant chain belongs to
+//                        the query; the table covers the part with the most
+//                        chunk ordinals)
+//   2. grouped scan      k_scan_group: k_scan_small's PROBE tiles of every
+//                        fused part -> dense raw values [nq][sum n_p]
+//   3. grouped select    k_select_group: k_final_select's body per (part,
+//                        query) over the part's slice -> per-part top-k lists
+//   4. merge             k_merge_shards (part merge) with the list index out
+// Parts the fused route does not take run mqvs_search's own path on the same
+// stream into their list of the same merge.  Nothing here depends on what a
+// kernel found: the call has one host wait, after the merge.
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <chrono>
+#include <vector>
+
+#include "workspace.h"
+
+struct mqvs_part_group {
+    std::vector<mqvs_segment *> segs;
+    int device = 0;
+    int d = 0;
+    bool cos = false;
+    int64_t rows = 0;
+};
+
+namespace mqvs {
+
+constexpr int64_t kGroupRowsMax = (int64_t)1 << 24;  // a part's slice is indexed by int
+// the fused route's row limit (mqvs_set_part_group_rows).  Measured with
+// groups of 8 equal parts, d 768, k 100 (profiles/part_group): fused wins up
+// to 131072 rows at nq 1 and nq 16, the per-part route (bf16 pre-filter, half
+// the bytes) from 262144 rows at nq 1 and from 524288 at nq 16
+static std::atomic<int64_t> g_group_rows{131072};
+static thread_local mqvs_part_group_stats t_group_stats{};
+
+static bool rows_fusable(const mqvs_segment *s, int64_t limit) { return !s->rows_host && s->n <= limit; }
+
+static int64_t part_ords(const mqvs_segment *s) {
+    return s->row_offset / s->granule + (s->n + s->granule - 1) / s->granule;
+}
+
+static mqvs_part_group *group_create(const mqvs_segment_t *segs, int nparts) {
+    if (nparts < 1 || !segs) fail(MQVS_ERR_BAD_ARGUMENTS, "a part group needs at least one segment");
+    for (int p = 0; p < nparts; ++p)
+        if (!segs[p]) fail(MQVS_ERR_BAD_ARGUMENTS, "null segment in a part group");
+    for (int p = 0; p < nparts; ++p) {
+        const mqvs_segment *s = segs[p];
+        if (s->binary) fail(MQVS_ERR_LOGICAL, "binary (FixedString) segment in a part group: groups hold Float32 parts");
+        if (s->d != segs[0]->d) fail(MQVS_ERR_LOGICAL, "segments of a part group differ in dimension");
+        if ((s->metric == MQVS_METRIC_COSINE) != (segs[0]->metric == MQVS_METRIC_COSINE))
+            fail(MQVS_ERR_LOGICAL, "cosine and non-cosine segments in one part group");
+        if (s->device != segs[0]->device) fail(MQVS_ERR_BAD_ARGUMENTS, "segments of a part group are on different devices");
+    }
+    auto *g = new mqvs_part_group();
+    g->segs.assign(segs, segs + nparts);
+    g->device = segs[0]->device;
+    g->d = segs[0]->d;
+    g->cos = segs[0]->metric == MQVS_METRIC_COSINE;
+    for (int p = 0; p < nparts; ++p) g->rows += segs[p]->n;
+    return g;
+}
+
+// 16-B aligned offsets of the staged bitmaps in one buffer
+static size_t bitmap_slot(size_t &total, int64_t n) {
+    const size_t off = total;
+    total += (size_t)round_up((n + 7) / 8, 16);
+    return off;
+}
+
+static void group_search(mqvs_part_group *g, const float *queries, int nq, int k, int metric,
+                         const uint8_t *const *filters, const uint8_t *const *exists, int32_t *out_part,
+                         int64_t *out_ids, float *out_dist, uint32_t flags, hipStream_t user_stream) {
+    check_search_args(g, "part group", nullptr, nq, k, queries, out_ids, out_dist);
+    if (nq > 0 && k > 0 && !out_part) fail(MQVS_ERR_BAD_ARGUMENTS, "null query or output pointer");
+    const bool cos = metric == MQVS_METRIC_COSINE;
+    if (metric != MQVS_METRIC_L2 && metric != MQVS_METRIC_IP && !cos)
+        fail(MQVS_ERR_NOT_IMPLEMENTED, "Metric not implemented in brute force search for Float32 Vector");
+    if (cos != g->cos)
+        fail(MQVS_ERR_LOGICAL, "part group was prepared for a different metric (cosine segments are "
+                               "normalised in HBM and serve only cosine searches)");
+    const int nparts = (int)g->segs.size();
+    if ((int64_t)nparts * k > ((int64_t)1 << 20)) fail(MQVS_ERR_BAD_ARGUMENTS, "nparts * k above 2^20");
+    mqvs_part_group_stats st{};
+    st.parts = nparts;
+    st.nq = nq;
+    st.k = k;
+    t_group_stats = st;
+    if (nq == 0 || k == 0) return;
+    const bool timing = timing_on(flags);
+    const auto t0 = std::chrono::steady_clock::now();
+
+    DeviceGuard guard(g->device);
+    Workspace &ws = workspace(g->device);
+    WsCall ws_call(ws);
+    hipStream_t s = user_stream ? user_stream : ws.stream;
+    ws.last = s;
+    const bool dev = flags & MQVS_F_DEVICE_PTRS;
+    const int d = g->d;
+    const int64_t qstride = round_up(d, 32);
+
+    // ---- the routes.  Cosine: the variant table holds maxv variants per
+    // query; a part of more chunk ordinals is fused only while the table
+    // grown to them stays within the scratch budget (and kMaxVariantsCap)
+    const int64_t limit = g_group_rows.load(std::memory_order_relaxed);
+    const int64_t maxv_fit =
+        std::min<int64_t>(kMaxVariantsCap, (int64_t)(scratch_budget() / (sizeof(float) * (size_t)nq * qstride)));
+    std::vector<char> fused(nparts, 0);
+    int nfused = 0, maxv = cos ? kMaxVariants : 1;
+    for (int p = 0; p < nparts; ++p) {
+        const mqvs_segment *seg = g->segs[p];
+        bool f = nq < kBlasThreshold && k <= kSortCap && rows_fusable(seg, limit);
+        if (f && cos) {
+            if (filters && filters[p]) f = false;  // (its chunk ordinals come from the filter)
+            const int64_t o = part_ords(seg);
+            if (o > kMaxVariants && o > maxv_fit) f = false;
+            if (f) maxv = (int)std::max<int64_t>(maxv, o);
+        }
+        fused[p] = f;
+        nfused += f;
+        if (f) st.fused_rows += seg->n;
+    }
+    st.fused_parts = nfused;
+    st.looped_parts = nparts - nfused;
+
+    // ---- inputs.  Host bitmaps: every part's into one pinned buffer behind
+    // the slot tables, one copy to the device
+    const float *dq =
+        (const float *)ws.io.in(queries, sizeof(float) * (size_t)nq * d, nullptr, nullptr, 0, dev, s).queries;
+    // slices of fused parts whose dense matrix fits the scratch budget
+    struct Slice {
+        int first_slot, nslots;
+        int64_t tiles, cols;
+    };
+    std::vector<Slice> slices;
+    std::vector<GroupSlot> slots;
+    const int64_t max_cols = std::max<int64_t>(1, (int64_t)(scratch_budget() / (sizeof(float) * (size_t)nq)));
+    std::vector<size_t> foff(nparts, (size_t)-1), eoff(nparts, (size_t)-1);
+    size_t bits_bytes = 0;
+    if (!dev)
+        for (int p = 0; p < nparts; ++p) {
+            if (filters && filters[p]) foff[p] = bitmap_slot(bits_bytes, g->segs[p]->n);
+            if (exists && exists[p]) eoff[p] = bitmap_slot(bits_bytes, g->segs[p]->n);
+        }
+    {
+        Slice cur{0, 0, 0, 0};
+        auto close = [&] {
+            if (cur.nslots == 0) return;
+            GroupSlot end{};
+            end.tile0 = cur.tiles;
+            end.col0 = cur.cols;
+            end.part = -1;
+            slots.push_back(end);
+            slices.push_back(cur);
+            cur = Slice{(int)slots.size(), 0, 0, 0};
+        };
+        for (int p = 0; p < nparts; ++p) {
+            if (!fused[p]) continue;
+            const mqvs_segment *seg = g->segs[p];
+            if (cur.nslots > 0 && cur.cols + seg->n > max_cols) close();
+            GroupSlot e{};
+            e.rows = seg->rows;
+            e.chunk_ord = seg->chunk_ord;
+            e.nonempty = seg->nonempty_bits;
+            e.n = seg->n;
+            e.granule = seg->granule;
+            e.row_offset = seg->row_offset;
+            e.tile0 = cur.tiles;
+            e.col0 = cur.cols;
+            e.part = p;
+            // cosine and chunk-ordinal parts: tiles that never span two chunks
+            const bool aligned = cos || seg->chunk_ord != nullptr;
+            int64_t tiles = (seg->n + kSmallRows - 1) / kSmallRows;
+            if (aligned && seg->n > 0) {
+                // (a part shorter than its granule is one chunk: no tiles past its rows)
+                e.tiles_per_chunk = (std::min(seg->granule, seg->n) + kSmallRows - 1) / kSmallRows;
+                tiles = (seg->n + seg->granule - 1) / seg->granule * e.tiles_per_chunk;
+            }
+            slots.push_back(e);
+            cur.nslots += 1;
+            cur.tiles += tiles;
+            cur.cols += seg->n;
+        }
+        close();
+    }
+    const size_t slot_bytes = (size_t)round_up((int64_t)(sizeof(GroupSlot) * slots.size()), 16);
+    const uint8_t *dbits = nullptr;
+    const GroupSlot *dslots = nullptr;
+    if (slot_bytes + bits_bytes > 0) {
+        auto *pin = (unsigned char *)ws.pg_pin_in.get(slot_bytes + bits_bytes);
+        auto *dbuf = (unsigned char *)ws.pg_slots.get(slot_bytes + bits_bytes);
+        dslots = (const GroupSlot *)dbuf;
+        dbits = dbuf + slot_bytes;
+        for (int p = 0; p < nparts && !dev; ++p) {
+            const size_t bm = (size_t)((g->segs[p]->n + 7) / 8);
+            if (foff[p] != (size_t)-1) std::memcpy(pin + slot_bytes + foff[p], filters[p], bm);
+            if (eoff[p] != (size_t)-1) std::memcpy(pin + slot_bytes + eoff[p], exists[p], bm);
+        }
+        // this call's bitmaps of part p on the device
+        for (GroupSlot &e : slots) {
+            if (e.part < 0) continue;
+            const int p = e.part;
+            e.filter = !(filters && filters[p]) ? nullptr : dev ? filters[p] : dbits + foff[p];
+            e.exists = !(exists && exists[p]) ? nullptr : dev ? exists[p] : dbits + eoff[p];
+        }
+        if (!slots.empty()) std::memcpy(pin, slots.data(), sizeof(GroupSlot) * slots.size());
+        MQVS_HIP(hipMemcpyAsync(dbuf, pin, slot_bytes + bits_bytes, hipMemcpyHostToDevice, s));
+    }
+    auto part_filter = [&](int p) -> const uint8_t * {
+        return !(filters && filters[p]) ? nullptr : dev ? filters[p] : dbits + foff[p];
+    };
+    auto part_exists = [&](int p) -> const uint8_t * {
+        return !(exists && exists[p]) ? nullptr : dev ? exists[p] : dbits + eoff[p];
+    };
+
+    // ---- per-part lists [nparts][nq][k] and the outputs
+    const size_t nlist = (size_t)nparts * nq * k, nout = (size_t)nq * k;
+    auto *lbuf = (unsigned char *)ws.pg_lists.get(nlist * 12 + 16);
+    auto *list_ids = (int64_t *)lbuf;
+    auto *list_dist = (float *)(lbuf + nlist * 8);
+    const CallIO::Out out = ws.io.out(nout, dev, out_ids, out_dist);
+    int32_t *dpart = dev ? out_part : (int32_t *)ws.pg_part.get(sizeof(int32_t) * nout);
+
+    // ---- the fused route
+    if (nfused > 0) {
+        // [overflow 4][status 4][qmu nq][qlam nq][qnorms nq]
+        int *fl = (int *)ws.pg_q.get(sizeof(int) * (8 + 3 * (size_t)nq));
+        launch_fill2((uint32_t *)fl, 8, 0u, nullptr, 0, 0u, s);
+        int *qmu = fl + 8, *qlam = qmu + nq;
+        float *qnorms = (float *)(qlam + nq);
+        float *qvars = (float *)ws.pg_qvars.get(sizeof(float) * (size_t)nq * maxv * qstride);
+        // (a chain that does not repeat within maxv steps sets fl[4]: every
+        // fused part has at most maxv chunk ordinals, so none reads past it)
+        launch_query_prep(dq, nq, d, cos ? MQVS_METRIC_COSINE : MQVS_METRIC_L2, false, qvars, maxv, qnorms, qmu, qlam,
+                          fl + 4, s);
+        MQVS_HIP(hipGetLastError());
+        st.launches += 2;
+        int64_t ld = 0;
+        for (const Slice &sl : slices) ld = std::max(ld, sl.cols);
+        float *matrix = (float *)ws.pg_matrix.get(sizeof(float) * (size_t)nq * std::max<int64_t>(ld, 1));
+        ScanParams p{};
+        p.d = d;
+        p.nq = nq;
+        p.qvars = qvars;
+        p.qnorms = qnorms;
+        p.qmu = qmu;
+        p.qlam = qlam;
+        p.maxv = maxv;
+        p.blas_nq = nq;
+        p.probe = matrix;
+        for (const Slice &sl : slices) {
+            p.probe_ld = sl.cols;
+            if (sl.tiles > 0) {
+                launch_scan_group(p, dslots + sl.first_slot, sl.nslots, sl.tiles, metric, s);
+                MQVS_HIP(hipGetLastError());
+                st.launches += 1;
+            }
+            launch_select_group(matrix, sl.cols, dslots + sl.first_slot, sl.nslots, nq, k, metric, list_ids, list_dist,
+                                fl, s);
+            MQVS_HIP(hipGetLastError());
+            st.launches += 1;
+        }
+    }
+
+    // ---- the per-part route (each search ends in its own host wait)
+    for (int p = 0; p < nparts; ++p) {
+        if (fused[p]) continue;
+        search_segment(g->segs[p], dq, nq, k, metric, part_filter(p), part_exists(p), list_ids + (size_t)p * nq * k,
+                       list_dist + (size_t)p * nq * k, flags & ~(uint32_t)MQVS_F_ASYNC, s, -1);
+    }
+
+    // ---- the merge, and the call's one wait
+    uint4 *scratch = (int64_t)nparts * k > kSortCap
+                         ? (uint4 *)ws.pg_sort.get(sizeof(uint4) * 2 * (size_t)nparts * k * nq)
+                         : nullptr;
+    launch_merge_shards(nparts, nq, k, metric, list_ids, list_dist, out.ids, out.dist, true, scratch, s, dpart);
+    MQVS_HIP(hipGetLastError());
+    st.launches += 1;
+    ws.io.finish_begin(out, s);
+    int32_t *hpart = nullptr;
+    if (!dev) {
+        hpart = (int32_t *)ws.pg_pin_out.get(sizeof(int32_t) * nout);
+        MQVS_HIP(hipMemcpyAsync(hpart, dpart, sizeof(int32_t) * nout, hipMemcpyDeviceToHost, s));
+    }
+    host_wait(s);
+    ws.io.finish_end(out);
+    if (hpart) std::memcpy(out_part, hpart, sizeof(int32_t) * nout);
+    if (timing)
+        st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    t_group_stats = st;
+}
+
+}  // namespace mqvs
+
+using namespace mqvs;
+
+extern "C" {
+
+int mqvs_part_group_create(const mqvs_segment_t *segs, int32_t nparts, mqvs_part_group_t *out) {
+    return guarded([&] {
+        if (!out) fail(MQVS_ERR_BAD_ARGUMENTS, "null output handle");
+        *out = nullptr;
+        *out = group_create(segs, nparts);
+    });
+}
+
+int mqvs_part_group_free(mqvs_part_group_t group) {
+    return guarded([&] { delete group; });
+}
+
+int mqvs_part_group_info(mqvs_part_group_t group, int32_t *nparts, int64_t *rows, int32_t *d, int32_t *fusable_parts,
+                         size_t *hbm_bytes) {
+    return guarded([&] {
+        if (!group) fail(MQVS_ERR_BAD_ARGUMENTS, "null part group");
+        if (nparts) *nparts = (int32_t)group->segs.size();
+        if (rows) *rows = group->rows;
+        if (d) *d = group->d;
+        if (fusable_parts) {
+            const int64_t limit = g_group_rows.load(std::memory_order_relaxed);
+            int32_t f = 0;
+            for (const mqvs_segment *s : group->segs) f += rows_fusable(s, limit);
+            *fusable_parts = f;
+        }
+        if (hbm_bytes) *hbm_bytes = 0;
+    });
+}
+
+int mqvs_part_group_search(mqvs_part_group_t group, const float *queries, int32_t nq, int32_t k, int32_t metric,
+                           const uint8_t *const *filters, const uint8_t *const *row_exists, int32_t *out_part,
+                           int64_t *out_ids, float *out_dist, uint32_t flags, mqvs_stream_t stream) {
+    return guarded([&] {
+        fault_point();
+        WaitScope wsc{9, (uint64_t)(uintptr_t)group, (uint64_t)nq, (uint64_t)k, (uint64_t)metric, filters != nullptr,
+                      row_exists != nullptr, flags};
+        group_search(group, queries, nq, k, metric, filters, row_exists, out_part, out_ids, out_dist, flags,
+                     (hipStream_t)stream);
+    });
+}
+
+int mqvs_part_group_last_stats(mqvs_part_group_stats *out) {
+    if (!out) return MQVS_ERR_BAD_ARGUMENTS;
+    *out = t_group_stats;
+    return MQVS_OK;
+}
+
+int64_t mqvs_set_part_group_rows(int64_t rows) {
+    const int64_t prev = g_group_rows.load(std::memory_order_relaxed);
+    if (rows > 0) g_group_rows.store(std::min<int64_t>(rows, kGroupRowsMax), std::memory_order_relaxed);
+    return prev;
+}
+
+}  // extern "C"

@@ -23,6 +23,10 @@ struct Workspace {
     CallIO io;                       // staged inputs and outputs of host-pointer calls
     GBuf qvars, qnorms, qmu, qlam, status, ord, probe, tau, count, cand, overflow, misc, qhi, bq, thr, cand2, count2,
         gcount, goff, glist, large, sticky, surv, recs, flags, p4q, qord;
+    // part-group searches (part_group.hip) keep their own buffers: the
+    // per-part searches nested in such a call use the ones above
+    GBuf pg_q, pg_qvars, pg_slots, pg_bits, pg_matrix, pg_lists, pg_sort, pg_part;
+    HostBuf pg_pin_in, pg_pin_out;  // pinned staging: slot table + bitmaps; out_part
     int *host_flags = nullptr;  // pinned (64 ints; the selected-row count record at kCountRec)
     int64_t count_gen = 0;      // generation of the last selected-row count record asked for
     bool pending_timing = false, pending_bf16 = false;  // search_collect_stats
