@@ -598,6 +598,13 @@ __global__ __launch_bounds__(64) void k_decode_blocks(const uint8_t *src, int64_
             // the next chunk holding a token start
             ncs = E - E % kChunk > cs ? E - E % kChunk : cs + kChunk;
             __builtin_amdgcn_wave_barrier();
+            // the stream ends with the literals-only sequence, the only
+            // record without a match: one that ends in a match is malformed,
+            // as in the token path and the reference
+            if (done && (R == 0 || recs[R - 1].w != 0)) {
+                bad = true;
+                break;
+            }
             // ---- run the records, up to 64 at a time
             for (int32_t r0 = 0; r0 < R;) {
                 r0 = __builtin_amdgcn_readfirstlane(r0);
@@ -919,32 +926,39 @@ __global__ __launch_bounds__(64) void k_block_checksum(const uint8_t *src, const
 // ---- array sizes -> element offsets (exclusive scan over n UInt64) ----------
 constexpr int kScanTile = 4096;  // sizes per workgroup (256 threads x 16)
 
-__global__ __launch_bounds__(256) void k_sizes_partial(const uint64_t *sizes, int64_t n, int d, int64_t *tile_sum,
-                                                       int64_t *stats) {
+// (a size above max_size, the data stream's element count, cannot be right;
+// counted, since sizes that large can sum to the right total modulo 2^64)
+__global__ __launch_bounds__(256) void k_sizes_partial(const uint64_t *sizes, int64_t n, int d, uint64_t max_size,
+                                                       int64_t *tile_sum, int64_t *stats) {
     __shared__ int64_t red[256];
     __shared__ int64_t cnt[256];
+    __shared__ int64_t big[256];
     const int64_t base = (int64_t)blockIdx.x * kScanTile;
-    int64_t s = 0, notd = 0;
+    int64_t s = 0, notd = 0, over = 0;
     for (int i = threadIdx.x; i < kScanTile; i += 256) {
         const int64_t r = base + i;
         if (r < n) {
             s += (int64_t)sizes[r];
             notd += sizes[r] != (uint64_t)d;
+            over += sizes[r] > max_size;
         }
     }
     red[threadIdx.x] = s;
     cnt[threadIdx.x] = notd;
+    big[threadIdx.x] = over;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if (threadIdx.x < o) {
             red[threadIdx.x] += red[threadIdx.x + o];
             cnt[threadIdx.x] += cnt[threadIdx.x + o];
+            big[threadIdx.x] += big[threadIdx.x + o];
         }
         __syncthreads();
     }
     if (threadIdx.x == 0) {
         tile_sum[blockIdx.x] = red[0];
         if (cnt[0]) atomicAdd((unsigned long long *)&stats[0], (unsigned long long)cnt[0]);
+        if (big[0]) atomicAdd((unsigned long long *)&stats[2], (unsigned long long)big[0]);
     }
 }
 
@@ -1038,11 +1052,13 @@ void launch_block_checksum(const uint8_t *src, const IngestBlock *tab, int64_t n
 }
 
 // offsets[n] (exclusive); stats[0] += rows whose size != d, stats[1] = total
-// elements (stats zeroed by the caller); scratch >= ceil(n / 4096) int64
-void launch_sizes_scan(const uint64_t *sizes, int64_t n, int d, int64_t *offsets, int64_t *scratch, int64_t *stats,
-                       hipStream_t s) {
+// elements, stats[2] += rows whose size > max_size (stats zeroed by the
+// caller); scratch >= ceil(n / 4096) int64
+void launch_sizes_scan(const uint64_t *sizes, int64_t n, int d, int64_t max_size, int64_t *offsets, int64_t *scratch,
+                       int64_t *stats, hipStream_t s) {
     const int64_t tiles = std::max<int64_t>(1, (n + kScanTile - 1) / kScanTile);
-    hipLaunchKernelGGL(k_sizes_partial, dim3((unsigned)tiles), dim3(256), 0, s, sizes, n, d, scratch, stats);
+    hipLaunchKernelGGL(k_sizes_partial, dim3((unsigned)tiles), dim3(256), 0, s, sizes, n, d, (uint64_t)max_size, scratch,
+                       stats);
     hipLaunchKernelGGL(k_sizes_top, dim3(1), dim3(1024), 0, s, scratch, tiles, stats);
     hipLaunchKernelGGL(k_sizes_final, dim3((unsigned)tiles), dim3(256), 0, s, sizes, n, scratch, offsets);
 }

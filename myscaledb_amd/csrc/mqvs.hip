@@ -823,10 +823,10 @@ static mqvs_segment *ingest_column(const uint8_t *data_bin, int64_t data_bytes, 
         auto *scratch = (int64_t *)tmp.alloc(sizeof(int64_t) * (size_t)tiles);
         auto *st = (int64_t *)tmp.alloc(sizeof(int64_t) * 4);
         MQVS_HIP(hipMemsetAsync(st, 0, sizeof(int64_t) * 4, s));
-        if (n > 0) launch_sizes_scan(sizes, n, d, offs, scratch, st, s);
+        if (n > 0) launch_sizes_scan(sizes, n, d, dt.second / 4, offs, scratch, st, s);
         MQVS_HIP(hipGetLastError());
-        MQVS_HIP(hipMemcpyAsync(h, st, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        int *hstatus = reinterpret_cast<int *>(h + 2);
+        MQVS_HIP(hipMemcpyAsync(h, st, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        int *hstatus = reinterpret_cast<int *>(h + 3);
         if (verify) MQVS_HIP(hipStreamWaitEvent(s, tmp.join, 0));
         MQVS_HIP(hipMemcpyAsync(hstatus, status, sizeof(int), hipMemcpyDeviceToHost, s));
         host_wait(s);
@@ -837,6 +837,9 @@ static mqvs_segment *ingest_column(const uint8_t *data_bin, int64_t data_bytes, 
         if (*hstatus)
             fail(MQVS_ERR_ILLEGAL_COLUMN, "malformed LZ4 block (CANNOT_DECOMPRESS)");
         const int64_t notd = h[0], nelem = h[1];
+        if (h[2])  // (such sizes can sum to the right count modulo 2^64)
+            fail(MQVS_ERR_ILLEGAL_COLUMN, std::to_string(h[2]) + " array sizes exceed the " +
+                                              std::to_string(dt.second / 4) + " elements of the data stream");
         if (nelem * 4 != dt.second)
             fail(MQVS_ERR_ILLEGAL_COLUMN, "array sizes sum to " + std::to_string(nelem) + " elements, the data stream "
                                               "holds " + std::to_string(dt.second / 4));

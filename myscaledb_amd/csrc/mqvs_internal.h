@@ -379,8 +379,8 @@ void launch_decode_blocks(const uint8_t *src, int64_t src_bytes, const IngestBlo
 // hash_out (optional) receives [nblocks][2] (low, high)
 void launch_block_checksum(const uint8_t *src, const IngestBlock *tab, int64_t nblocks, int flag, int *status,
                            uint64_t *hash_out, hipStream_t s);
-void launch_sizes_scan(const uint64_t *sizes, int64_t n, int d, int64_t *offsets, int64_t *scratch, int64_t *stats,
-                       hipStream_t s);
+void launch_sizes_scan(const uint64_t *sizes, int64_t n, int d, int64_t max_size, int64_t *offsets, int64_t *scratch,
+                       int64_t *stats, hipStream_t s);
 void launch_array_rows(const float *data, const int64_t *offsets, const uint64_t *sizes, int64_t n, int d,
                        float *rows, uint8_t *nonempty, hipStream_t s);
 

@@ -3,11 +3,11 @@ oracle: the decoded rows are bit-identical to the oracle's decode + copy loop
 (MergeTreeVSManager.cpp:1381-1393), and searches over the ingested segment
 equal the oracle's vectorScanWithoutIndex on those rows."""
 import ctypes
-import struct
 
 import numpy as np
 import pytest
 
+import lz4_streams as L
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -152,9 +152,7 @@ def _corrupt(db, what):
 def _hand_block(offset):
     """12 bytes = 3 floats: literal "abcd", a 4-byte match at `offset`, last
     literals "wxyz" (LZ4 block format)."""
-    blk = bytes([0x40]) + b"abcd" + struct.pack("<H", offset) + bytes([0x40]) + b"wxyz"
-    body = struct.pack("<BII", 0x82, 9 + len(blk), 12) + blk
-    return O.checksum_bytes(body) + body
+    return L.frame(L.seq_bytes(b"abcd", offset, 4) + L.seq_bytes(b"wxyz"), 12)
 
 
 def test_gpu_ingest_hand_built_lz4(mq):
