@@ -1,6 +1,7 @@
-// index_internal.h -- what the index path's files share: index.hip (build,
-// auto-tuning, binary index, C glue), index_search.hip (the float index
-// search) and index_blob.hip (save / load).
+// index_internal.h -- what the index path's files share: index.hip (the
+// thread's workspace, the parameter parser, C glue), index_build.hip (the
+// builds), index_search.hip and index_search_binary.hip (the float and the
+// binary index search) and index_blob.hip (save / load).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -77,7 +78,7 @@ struct ListBufs {
 };
 
 // The scratch of a thread's index searches.  Every buffer is a GBuf: it grows
-// through the thread's FLAT workspace gate (WsScope in search_index_impl), so
+// through the thread's FLAT workspace gate (the WsScope of SearchAdmission), so
 // concurrent index searches share the process-wide HBM budget with FLAT
 // scans, and an idle thread's index scratch is trimmed with its workspace.
 struct IndexWorkspace final : WsExt {
@@ -175,18 +176,44 @@ double num_param(const std::map<std::string, std::string> &m, const std::string 
 void check_keys(const std::map<std::string, std::string> &m, const std::vector<std::string> &valid, const char *what);
 int nprobe_of(const mqvs_index *ix, double alpha);
 void free_index(mqvs_index *ix);
+
+// ---- index_build.hip
+mqvs_index *build_impl(mqvs_segment *seg, const char *index_type, const char *params);
+// a binary metric by name (`what`: the parameter, for the message)
+int binary_metric_of(const std::string &name, const char *what);
 void check_index_width(mqvs_segment *seg);
 void finish_index(mqvs_index *ix, const int32_t *assign, bool from_blob, hipStream_t s);
 
 // ---- index_search.hip
-extern thread_local int64_t *t_probes_out;  // mqvs_index_probes
+// The admission of one search to the thread's workspace on the segment's
+// device: the workspace's budget gate (every scratch buffer of the stages
+// grows through it) is held, and the search's stream named to it, for the
+// scope's life.
+struct SearchAdmission {
+    DeviceGuard guard;
+    IndexWorkspace &ws;
+    WsScope scope;
+    const hipStream_t s;
+    SearchAdmission(mqvs_segment *seg, hipStream_t user_stream)
+        : guard(seg->device), ws(index_workspace(seg->device)), scope(seg->device, &ws),
+          s(user_stream ? user_stream : thread_stream(seg->device)) {
+        scope.set_stream(s);
+    }
+};
+int search_nprobe(const mqvs_index *ix, const std::map<std::string, std::string> &pm);
+void index_read_stats(IndexWorkspace &ws, mqvs_index_search_stats st, bool tev, bool binary);
 void search_index_impl(mqvs_index *ix, const float *queries, int nq, int k, const char *params, const uint8_t *filter,
                        const uint8_t *exists, int64_t *out_ids, float *out_dist, uint32_t flags,
                        hipStream_t user_stream, int formula_nq, int maxv_hint = 0, int64_t ord_base = -1,
-                       int *async_word = nullptr);
+                       int *async_word = nullptr, int64_t *probes_out = nullptr);
 // the stats of this thread's last ASYNC search with a flag word of the
 // caller's (sharded.hip's fast path), after the caller's stream sync
 void index_collect_stats(int device);
+
+// ---- index_search_binary.hip
+void search_binary_index_impl(mqvs_index *ix, const uint8_t *queries, int nq, int k, const char *params,
+                              const uint8_t *filter, const uint8_t *exists, int64_t *out_ids, float *out_dist,
+                              uint32_t flags, hipStream_t user_stream, int64_t *probes_out);
 
 // ---- index_blob.hip
 size_t blob_bytes(const mqvs_index *ix);

@@ -1,5 +1,7 @@
 // index_search.hip -- the float index search of libmqvs (mqvs_index_search,
-// mqvs_index_probes; the index itself, its build and the C glue: index.hip).
+// mqvs_index_probes; the build: index_build.hip, the C glue: index.hip), and
+// what it shares with the binary index search (index_search_binary.hip): the
+// nprobe resolution and the stats read.
 //
 // Search:
 //   coarse   FLAT search of the queries against the centroid segment, k =
@@ -223,10 +225,6 @@ static ListStats list_pass(ListBufs &b, const ListLayout &l, const ListArgs &a) 
     return ListStats{p.stats, pairs};
 }
 
-// mqvs_index_probes sets this for the duration of one search: the coarse
-// step's probes[nq][nprobe] are copied there and the search ends
-thread_local int64_t *t_probes_out = nullptr;
-
 // ---- the search of one query batch --------------------------------------------
 // Stages over the search's state, as FlatSearch (search.hip): run() queues
 // them in order on one stream; every stage reads what earlier ones left in
@@ -251,6 +249,9 @@ struct IndexSearch {
     // lower ranks' searched chunks were counted), else row_offset / granule
     const int64_t ord_base;
     int *const async_word;  // ASYNC: where the outcome flags go (null: the thread's sticky word)
+    // mqvs_index_probes: the coarse step's probes[nq][nprobe] are copied
+    // there and the search ends
+    int64_t *const probes_out;
     // ---- derived constants
     const int d;
     const bool dev, async, cos, first_stage, fp8;
@@ -303,11 +304,11 @@ struct IndexSearch {
     IndexSearch(mqvs_index *index, IndexWorkspace &w, hipStream_t stream, const float *q, int nq_, int k_,
                 const uint8_t *filter_, const uint8_t *exists_, int64_t *ids, float *dist, uint32_t flags_, int fnq_,
                 int nprobe_, int R_, int maxv_hint, int64_t ord_base_, int *async_word_,
-                const mqvs_index_search_stats &header)
+                int64_t *probes_out_, const mqvs_index_search_stats &header)
         : ix(index), seg(index->seg), ws(w), s(stream), queries(q), nq(nq_), k(k_), filter(filter_), exists(exists_),
           out_ids(ids), out_dist(dist), flags(flags_), fnq(fnq_), nprobe(nprobe_), R(R_),
           ord_base(ord_base_ >= 0 ? ord_base_ : index->seg->row_offset / index->seg->granule),
-          async_word(async_word_), d(seg->d),
+          async_word(async_word_), probes_out(probes_out_), d(seg->d),
           dev(flags_ & MQVS_F_DEVICE_PTRS), async(dev && (flags_ & MQVS_F_ASYNC)),
           cos(index->metric == MQVS_METRIC_COSINE), first_stage(flags_ & MQVS_F_FIRST_STAGE),
           fp8(index->plane_fmt == MQVS_INDEX_PLANE_FP8), tev(timing_on(flags_)), split(cos && !first_stage),
@@ -339,7 +340,7 @@ struct IndexSearch {
         prep_queries();
         quantise_queries();
         coarse();
-        if (t_probes_out) {
+        if (probes_out) {
             probes_only();
             return 0;
         }
@@ -529,7 +530,7 @@ void IndexSearch::coarse_list_pass() {
 
 // mqvs_index_probes: the coarse step's lists, nothing after it
 void IndexSearch::probes_only() {
-    MQVS_HIP(hipMemcpyAsync(t_probes_out, probes, sizeof(int64_t) * (size_t)nq * nprobe, hipMemcpyDeviceToHost, s));
+    MQVS_HIP(hipMemcpyAsync(probes_out, probes, sizeof(int64_t) * (size_t)nq * nprobe, hipMemcpyDeviceToHost, s));
     MQVS_HIP(hipMemcpyAsync(ws.host + 6, istat, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     host_wait(s);
     g_istats.pick_overflow = (int32_t)ws.host[6];
@@ -657,22 +658,25 @@ void IndexSearch::rerank() {
 }
 
 // the thread's stats from the pinned words of its last search (after the
-// wait that covers them)
-static void index_read_stats(IndexWorkspace &ws, mqvs_index_search_stats st, bool tev) {
+// wait that covers them).  A binary search has no plan, pick or re-rank: those
+// fields stay 0, and it records nothing between ev[4] and ev[5].
+void index_read_stats(IndexWorkspace &ws, mqvs_index_search_stats st, bool tev, bool binary) {
     const int64_t *hs = ws.host;
     st.values = hs[0];
     st.items = hs[1];
     st.plane_bytes = hs[2];
     st.pairs = hs[3];
-    st.pick_overflow = (int32_t)hs[6];  // (istat, copied with the status words)
-    st.reranked = hs[7];
+    if (!binary) {
+        st.pick_overflow = (int32_t)hs[6];  // (istat, copied with the status words)
+        st.reranked = hs[7];
+    }
     float t[5] = {0, 0, 0, 0, 0}, tot = 0;
     if (tev) {
-        for (int i = 0; i < 5; ++i) MQVS_HIP(hipEventElapsedTime(&t[i], ws.ev[i], ws.ev[i + 1]));
+        for (int i = 0; i < (binary ? 4 : 5); ++i) MQVS_HIP(hipEventElapsedTime(&t[i], ws.ev[i], ws.ev[i + 1]));
         MQVS_HIP(hipEventElapsedTime(&tot, ws.ev[0], ws.ev[5]));
     }
     st.coarse_ms = t[0];
-    st.plan_ms = t[1];
+    st.plan_ms = binary ? 0 : t[1];
     st.scan_ms = t[2];
     st.select_ms = t[3];
     st.rerank_ms = t[4];
@@ -715,7 +719,7 @@ int IndexSearch::finish_sync() {
     if (const int want = first_stage ? 0 : check_variant_chain(*hst, ords, maxv)) return want;
     ws.io.finish_end(out);
     ws.pending = false;
-    index_read_stats(ws, st, tev);
+    index_read_stats(ws, st, tev, false);
     return 0;
 }
 
@@ -726,7 +730,15 @@ void index_collect_stats(int device) {
     IndexWorkspace &ws = index_workspace(device);
     if (!ws.pending) return;
     ws.pending = false;
-    index_read_stats(ws, ws.pending_st, ws.pending_tev);
+    index_read_stats(ws, ws.pending_st, ws.pending_tev, false);
+}
+
+// nprobe of a search of either kind: the `nprobe` parameter, else from the
+// search's alpha (the `alpha` parameter, else the index's)
+int search_nprobe(const mqvs_index *ix, const std::map<std::string, std::string> &pm) {
+    const double alpha = num_param(pm, "alpha", ix->alpha, 1.0, 4.0);
+    return pm.count("nprobe") ? (int)num_param(pm, "nprobe", 1, 1, (double)std::min<int64_t>(ix->nlist, kSortCap))
+                              : nprobe_of(ix, alpha);
 }
 
 // The driver: resolves the search parameters, splits into query sub-batches
@@ -738,19 +750,19 @@ void index_collect_stats(int device) {
 // ord_base: the cosine chunk-ordinal base of a row-range shard (< 0:
 // row_offset / granule); the sub-batches and the re-run keep it.  async_word:
 // an ASYNC search's outcome flags go there instead of the sticky word.
+// probes_out (mqvs_index_probes): the search ends after the coarse step, whose
+// probes[nq][nprobe] are copied there.
 void search_index_impl(mqvs_index *ix, const float *queries, int nq, int k, const char *params, const uint8_t *filter,
                        const uint8_t *exists, int64_t *out_ids, float *out_dist, uint32_t flags,
-                       hipStream_t user_stream, int formula_nq, int maxv_hint, int64_t ord_base, int *async_word) {
+                       hipStream_t user_stream, int formula_nq, int maxv_hint, int64_t ord_base, int *async_word,
+                       int64_t *probes_out) {
     const int fnq = formula_nq > 0 ? formula_nq : nq;
     check_search_args(ix, "index", ix && ix->binary ? "binary index: search it with mqvs_index_search_binary" : nullptr,
                       nq, k, queries, out_ids, out_dist);
     const auto pm = parse_params(params);
     check_keys(pm, {"alpha", "nprobe", "num_reorder"}, "search");
     const bool first_stage = flags & MQVS_F_FIRST_STAGE;
-    const double alpha = num_param(pm, "alpha", ix->alpha, 1.0, 4.0);
-    const int nprobe = pm.count("nprobe")
-                           ? (int)num_param(pm, "nprobe", 1, 1, (double)std::min<int64_t>(ix->nlist, kSortCap))
-                           : nprobe_of(ix, alpha);
+    const int nprobe = search_nprobe(ix, pm);
     // num_reorder up to kSortCap sorts in LDS; above it (k > 2048 by default,
     // up to kLargeCap) through global scratch
     const int R = first_stage ? k
@@ -773,27 +785,22 @@ void search_index_impl(mqvs_index *ix, const float *queries, int nq, int k, cons
             for_query_batches(nq, qb, [&](int q0, int m) {
                 search_index_impl(ix, queries + (size_t)q0 * d, m, k, params, filter, exists,
                                   out_ids + (size_t)q0 * k, out_dist + (size_t)q0 * k, flags, user_stream, fnq, 0,
-                                  ord_base, async_word);
+                                  ord_base, async_word, probes_out ? probes_out + (size_t)q0 * nprobe : nullptr);
             });
+            // (the counters and times left are the last sub-batch's: the
+            // binary driver sums its sub-batches', this one never has)
             g_istats.nq = nq;
             return;
         }
     }
 
-    mqvs_segment *seg = ix->seg;
-    DeviceGuard guard(seg->device);
-    IndexWorkspace &ws = index_workspace(seg->device);
-    // admission under the workspace budget; every scratch buffer of the
-    // stages grows through its gate
-    WsScope scope(seg->device, &ws);
-    hipStream_t s = user_stream ? user_stream : thread_stream(seg->device);
-    scope.set_stream(s);
-    // (declared after the scope: its join guard runs before the scope is released)
-    IndexSearch search(ix, ws, s, queries, nq, k, filter, exists, out_ids, out_dist, flags, fnq, nprobe, R, maxv_hint,
-                       ord_base, async_word, st);
+    SearchAdmission adm(ix->seg, user_stream);
+    // (declared after the admission: its join guard runs before the scope is released)
+    IndexSearch search(ix, adm.ws, adm.s, queries, nq, k, filter, exists, out_ids, out_dist, flags, fnq, nprobe, R,
+                       maxv_hint, ord_base, async_word, probes_out, st);
     if (const int want = search.run())
         search_index_impl(ix, queries, nq, k, params, filter, exists, out_ids, out_dist, flags, user_stream, fnq, want,
-                          ord_base, async_word);
+                          ord_base, async_word, probes_out);
 }
 
 }  // namespace mqvs

@@ -461,7 +461,7 @@ void launch_exact_rerank(const ScanParams &p, int metric, const uint32_t *surv, 
                          hipStream_t s, const int *fl = nullptr, int *host_fl = nullptr);
 
 // ---------------------------------------------------------------------------
-// Index path (kernels_ivf.hip, index.hip)
+// Index path (kernels_ivf.hip, index_build.hip, index_search.hip)
 constexpr int kIvfPad = 16;  // list lengths padded to this many positions
 
 constexpr int kIvfChunk = 512;  // default list positions per scan work item (balances long and short lists)
@@ -582,7 +582,7 @@ void launch_words_to_host(const int64_t *a, int na, const int *b, int nb, int64_
 bool launch_scan_p4_groups(const ScanParams &p, int metric, hipStream_t s);
 void launch_centroid_mean(const float *rows, int d, const int32_t *order, const int64_t *off, int nlist, float *cent,
                           hipStream_t s);
-// Rows grouped by list on the device (kernels_ivf.hip; index.hip's
+// Rows grouped by list on the device (kernels_ivf.hip; index_build.hip's
 // finish_index).  assign[n]: list id of each row, -1 = in no list; a row whose
 // nonempty bit (may be null) is clear is in no list.
 // count: cnt[L] (zeroed) rows per list; *status (zeroed) |= kGrpBadRange for a
@@ -611,7 +611,7 @@ void launch_grp_canon(const int64_t *assign, int64_t n, int64_t L, const uint8_t
                       hipStream_t s);
 
 // ---------------------------------------------------------------------------
-// Binary index path (kernels_bivf.hip, index.hip)
+// Binary index path (kernels_bivf.hip, index_build.hip, index_search_binary.hip)
 struct BivfParams {
     const uint32_t *plane;    // [npos][code_words] codes in list order
     const int32_t *perm;      // [npos] part row of each position

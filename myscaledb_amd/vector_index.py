@@ -23,8 +23,9 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import F_ASYNC, F_DEVICE_PTRS, F_FIRST_STAGE, F_RERANK_ALL, check, lib
-from .vector_scan import BinaryVectorScanSegment, VectorScanSegment, _host_f32, _host_u8, _is_torch, _ptr
+from ._lib import F_DEVICE_PTRS, F_FIRST_STAGE, F_RERANK_ALL, check, lib
+from .vector_scan import (BinaryVectorScanSegment, VectorScanSegment, _host_f32, _host_u8, _is_torch, _ptr,
+                          _staged_search)
 
 
 def _params(p) -> bytes:
@@ -110,31 +111,13 @@ class VectorIndex:
         fs = (F_FIRST_STAGE if first_stage_only else 0) | (F_RERANK_ALL if rerank_all else 0)
         pr = _params(params)
         base = -1 if chunk_ord_base is None else int(chunk_ord_base)
-        if _is_torch(queries):
-            import torch
-            assert queries.is_cuda and queries.is_contiguous() and queries.dtype == torch.float32
-            nq = queries.shape[0]
-            if out is None:
-                ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
-                dist = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
-            else:
-                ids, dist = out
-            flags = F_DEVICE_PTRS | (F_ASYNC if async_ else 0) | fs
-            check(lib.mqvs_index_search_ex(self._h, _ptr(queries), nq, k, pr, _ptr(filter_bitmap), _ptr(row_exists),
-                                           base, _ptr(ids), _ptr(dist), flags,
-                                           ctypes.c_void_p(stream) if stream else None))
-            return ids, dist
-        q = _host_f32(queries)
-        if q.ndim == 1:
-            q = q[None, :]
-        nq = q.shape[0]
-        if q.shape[1] != self.segment.d:
-            raise _lib.MqvsError(_lib.ERR_LOGICAL, "The dimension of searched index and input doesn't match.")
-        ids = np.empty((nq, k), np.int64)
-        dist = np.empty((nq, k), np.float32)
-        check(lib.mqvs_index_search_ex(self._h, _ptr(q), nq, k, pr, _ptr(_host_u8(filter_bitmap)),
-                                       _ptr(_host_u8(row_exists)), base, _ptr(ids), _ptr(dist), fs, None))
-        return ids, dist
+
+        def call(qp, nq, fp, ep, ip, dp, flags, st):
+            check(lib.mqvs_index_search_ex(self._h, qp, nq, k, pr, fp, ep, base, ip, dp, flags | fs, st))
+
+        return _staged_search(queries, k, np.float32, self.segment.d,
+                              lambda got: "The dimension of searched index and input doesn't match.", filter_bitmap,
+                              row_exists, out, async_, stream, call)
 
     def save(self) -> bytes:
         """The index as one byte string (mqvs_index_save; VIWithColumnInPart::
@@ -235,30 +218,14 @@ class BinaryVectorIndex:
         exact, so first_stage_only returns the same result."""
         fs = F_FIRST_STAGE if first_stage_only else 0
         pr = _params(params)
-        if _is_torch(queries):
-            import torch
-            assert queries.is_cuda and queries.is_contiguous() and queries.dtype == torch.uint8
-            nq = queries.shape[0]
-            if queries.shape[1] != self.segment.nbytes:
-                raise _lib.MqvsError(_lib.ERR_LOGICAL, f"query length {queries.shape[1]} bytes != column "
-                                                       f"FixedString({self.segment.nbytes})")
-            if out is None:
-                ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
-                dist = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
-            else:
-                ids, dist = out
-            flags = F_DEVICE_PTRS | (F_ASYNC if async_ else 0) | fs
-            check(lib.mqvs_index_search_binary(self._h, _ptr(queries), nq, k, pr, _ptr(filter_bitmap),
-                                               _ptr(row_exists), _ptr(ids), _ptr(dist), flags,
-                                               ctypes.c_void_p(stream) if stream else None))
-            return ids, dist
-        q = self._host_queries(queries)
-        nq = q.shape[0]
-        ids = np.empty((nq, k), np.int64)
-        dist = np.empty((nq, k), np.float32)
-        check(lib.mqvs_index_search_binary(self._h, _ptr(q), nq, k, pr, _ptr(_host_u8(filter_bitmap)),
-                                           _ptr(_host_u8(row_exists)), _ptr(ids), _ptr(dist), fs, None))
-        return ids, dist
+
+        def call(qp, nq, fp, ep, ip, dp, flags, st):
+            check(lib.mqvs_index_search_binary(self._h, qp, nq, k, pr, fp, ep, ip, dp, flags | fs, st))
+
+        nb = self.segment.nbytes
+        return _staged_search(queries, k, np.uint8, nb,
+                              lambda got: f"query length {got} bytes != column FixedString({nb})", filter_bitmap,
+                              row_exists, out, async_, stream, call, torch_width_check=True)
 
     free = VectorIndex.free
 

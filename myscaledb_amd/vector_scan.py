@@ -65,6 +65,44 @@ def _host_u8(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.uint8)
 
 
+def _staged_search(queries, k, dtype, width, width_error, filter_bitmap, row_exists, out, async_, stream, call,
+                   torch_width_check=False):
+    """What every search method does around its C call: (ids[nq,k] int64,
+    dist[nq,k] float32) of call(qp, nq, fp, ep, ip, dp, flags, st).
+
+    torch CUDA queries go through as device pointers, into `out` (a pair of
+    tensors) or new tensors, on `stream`; async_ (device pointers only) adds
+    F_ASYNC.  Anything else is staged as a contiguous host array of `dtype`
+    (numpy float32 or uint8; one query may be 1-d) whose width must be `width`,
+    else MqvsError(LOGICAL_ERROR, width_error(got)); the device branch checks
+    the width only with torch_width_check."""
+    if _is_torch(queries):
+        import torch
+        assert queries.is_cuda and queries.is_contiguous() and queries.dtype == getattr(torch, dtype.__name__)
+        nq = queries.shape[0]
+        if torch_width_check and queries.shape[1] != width:
+            raise _lib.MqvsError(_lib.ERR_LOGICAL, width_error(queries.shape[1]))
+        if out is None:
+            ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
+            dist = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
+        else:
+            ids, dist = out
+        flags = F_DEVICE_PTRS | (F_ASYNC if async_ else 0)
+        call(_ptr(queries), nq, _ptr(filter_bitmap), _ptr(row_exists), _ptr(ids), _ptr(dist), flags,
+             ctypes.c_void_p(stream) if stream else None)
+        return ids, dist
+    q = np.ascontiguousarray(queries, dtype=dtype)
+    if q.ndim == 1:
+        q = q[None, :]
+    nq = q.shape[0]
+    if q.shape[1] != width:
+        raise _lib.MqvsError(_lib.ERR_LOGICAL, width_error(q.shape[1]))
+    ids = np.empty((nq, k), np.int64)
+    dist = np.empty((nq, k), np.float32)
+    call(_ptr(q), nq, _ptr(_host_u8(filter_bitmap)), _ptr(_host_u8(row_exists)), _ptr(ids), _ptr(dist), 0, None)
+    return ids, dist
+
+
 def pack_bitmap(mask) -> np.ndarray:
     """bool/0-1 per row -> LSB-first uint8 bitmap (Search::DenseBitmap byte layout)."""
     return np.packbits(np.asarray(mask, dtype=np.uint8), bitorder="little")
@@ -186,31 +224,9 @@ class VectorScanSegment:
         def call(qp, nq, fp, ep, ip, dp, flags, st):
             check(lib.mqvs_search_ex(self._h, qp, nq, k, m, fp, ep, base, ip, dp, flags | extra, st))
 
-        if _is_torch(queries):
-            import torch
-            assert queries.is_cuda and queries.is_contiguous() and queries.dtype == torch.float32
-            nq = queries.shape[0]
-            if out is None:
-                ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
-                dist = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
-            else:
-                ids, dist = out
-            flags = F_DEVICE_PTRS | (F_ASYNC if async_ else 0)
-            call(_ptr(queries), nq, _ptr(filter_bitmap), _ptr(row_exists), _ptr(ids), _ptr(dist), flags,
-                 ctypes.c_void_p(stream) if stream else None)
-            return ids, dist
-        q = _host_f32(queries)
-        if q.ndim == 1:
-            q = q[None, :]
-        nq = q.shape[0]
-        if q.shape[1] != self.d:
-            raise _lib.MqvsError(_lib.ERR_LOGICAL,
-                                 f"query dimension {q.shape[1]} != column dimension {self.d}")
-        ids = np.empty((nq, k), np.int64)
-        dist = np.empty((nq, k), np.float32)
-        call(_ptr(q), nq, _ptr(_host_u8(filter_bitmap)), _ptr(_host_u8(row_exists)), _ptr(ids),
-             _ptr(dist), 0, None)
-        return ids, dist
+        return _staged_search(queries, k, np.float32, self.d,
+                              lambda got: f"query dimension {got} != column dimension {self.d}", filter_bitmap,
+                              row_exists, out, async_, stream, call)
 
     def rerank(self, queries, candidates, k, metric=None, row_exists=None):
         """mqvs_rerank (computeTopDistanceSubset contract, VIWithDataPart.cpp:838-856):
@@ -284,31 +300,13 @@ class BinaryVectorScanSegment:
         """mqvs_search_binary: (ids[nq,k] int64, dist[nq,k] float32), ascending,
         -1 / FLT_MAX padded."""
         m = self.metric if metric is None else metric_id(metric)
-        if _is_torch(queries):
-            import torch
-            assert queries.is_cuda and queries.is_contiguous() and queries.dtype == torch.uint8
-            nq = queries.shape[0]
-            if out is None:
-                ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
-                dist = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
-            else:
-                ids, dist = out
-            flags = F_DEVICE_PTRS | (F_ASYNC if async_ else 0)
-            check(lib.mqvs_search_binary(self._h, _ptr(queries), nq, k, m, _ptr(filter_bitmap), _ptr(row_exists),
-                                         _ptr(ids), _ptr(dist), flags, ctypes.c_void_p(stream) if stream else None))
-            return ids, dist
-        q = _host_u8(queries)
-        if q.ndim == 1:
-            q = q[None, :]
-        nq = q.shape[0]
-        if q.shape[1] != self.nbytes:
-            raise _lib.MqvsError(_lib.ERR_LOGICAL,
-                                 f"query length {q.shape[1]} bytes != column FixedString({self.nbytes})")
-        ids = np.empty((nq, k), np.int64)
-        dist = np.empty((nq, k), np.float32)
-        check(lib.mqvs_search_binary(self._h, _ptr(q), nq, k, m, _ptr(_host_u8(filter_bitmap)),
-                                     _ptr(_host_u8(row_exists)), _ptr(ids), _ptr(dist), 0, None))
-        return ids, dist
+
+        def call(qp, nq, fp, ep, ip, dp, flags, st):
+            check(lib.mqvs_search_binary(self._h, qp, nq, k, m, fp, ep, ip, dp, flags, st))
+
+        return _staged_search(queries, k, np.uint8, self.nbytes,
+                              lambda got: f"query length {got} bytes != column FixedString({self.nbytes})",
+                              filter_bitmap, row_exists, out, async_, stream, call)
 
     def free(self):
         if self._h:

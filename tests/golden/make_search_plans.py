@@ -64,6 +64,9 @@ def index_cases():
     def ix(build, nq, params, metric="L2", k=K, **kw):
         return dict(kind="index", metric=metric, nq=nq, k=k, params=params, build=build, **kw)
 
+    def bx(nq, params, metric="Hamming", k=K, **kw):
+        return dict(kind="binary_index", metric=metric, nq=nq, k=k, params=params, build="nlist=64", **kw)
+
     return [dict(kind="index", metric="L2", nq=8, k=K, params="nprobe=8"),
             dict(kind="binary_index", metric="Hamming", nq=8, k=K, params="nprobe=8"),
             # pair mode (16 nq nprobe <= nlist), then the grouped plan with
@@ -98,7 +101,17 @@ def index_cases():
             ix("nlist=64,plane=fp8", 8, "nprobe=8", first_stage=True),
             ix("nlist=256,plane=fp8", 8, "nprobe=100"),
             # large k (num_reorder above kSortCap): query sub-batches under a 4 MiB scratch budget
-            ix("nlist=64", 20, "nprobe=8", k=5000, scratch_budget=4 << 20)]
+            ix("nlist=64", 20, "nprobe=8", k=5000, scratch_budget=4 << 20),
+            # binary index of the binary part (a Hamming part: Jaccard is the
+            # search's metric): ranked probes, every list (no ranking), a
+            # filter, k above kSortCap (the large select scratch), and query
+            # sub-batches under a 1 MiB scratch budget
+            bx(8, "nprobe=8"),
+            bx(8, "nprobe=8,metric=Jaccard", metric="Jaccard"),
+            bx(8, "nprobe=64"),
+            bx(8, "nprobe=8", sel=0.05),
+            bx(8, "nprobe=8", k=5000),
+            bx(20, "nprobe=8", scratch_budget=1 << 20)]
 
 
 def case_id(c):
@@ -144,12 +157,13 @@ class Parts:
         return self._segs["bin"]
 
     def index(self, kind, metric="L2", build=None):
-        key = (kind, metric, build)
+        # (a binary index is the Hamming part's whatever metric its search names)
+        key = (kind, metric if kind == "index" else "Hamming", build)
         if key not in self._idx:
             if kind == "index":
                 self._idx[key] = self.mq.VectorIndex.build(self.float_seg("main", metric), "MSTG", build)
             else:
-                self._idx[key] = self.mq.BinaryVectorIndex.build(self.binary_seg(), "BINARYMSTG")
+                self._idx[key] = self.mq.BinaryVectorIndex.build(self.binary_seg(), "BINARYMSTG", build)
         return self._idx[key]
 
     def free(self):
@@ -171,11 +185,11 @@ def search_index_case(parts, c):
     """The search of one index case; returns (ids, dist) as host arrays."""
     from myscaledb_amd import vector_scan
     idx = parts.index(c["kind"], c["metric"], c.get("build"))
-    if c["kind"] == "binary_index":
-        return idx.search(binary_queries(c["nq"]), c["k"], c["params"])
     flt = None if c.get("sel") is None else selection(idx.segment.n, c["sel"])
     prev = vector_scan.set_scratch_budget(c["scratch_budget"]) if c.get("scratch_budget") else None
     try:
+        if c["kind"] == "binary_index":
+            return idx.search(binary_queries(c["nq"]), c["k"], c["params"], filter_bitmap=flt)
         return idx.search(float_queries(c["nq"]), c["k"], c["params"], filter_bitmap=flt,
                           first_stage_only=bool(c.get("first_stage")), rerank_all=bool(c.get("rerank_all")))
     finally:

@@ -342,6 +342,58 @@ def test_binary_index_query_sub_batches(small):
     assert_same(ids_e, dist_e, ids_b, dist_b, "sub-batched exhaustive search")
 
 
+def test_binary_index_async(mq, small):
+    """An ASYNC device-pointer search into preallocated outputs: nothing is
+    flagged, and the ids and distance bits are the synchronous host-pointer
+    search's, with and without a row-ids map."""
+    import torch
+    idx, q, n = small["idx"], small["queries"], small["n"]
+    ids, dist = idx.search(q, 20, "nprobe=4")
+    dq = torch.from_numpy(q).cuda()
+    out = (torch.empty((len(q), 20), dtype=torch.int64, device="cuda"),
+           torch.empty((len(q), 20), dtype=torch.float32, device="cuda"))
+
+    def run_async(ctx, want_ids):
+        out[0].fill_(-7)
+        out[1].fill_(-7.0)
+        torch.cuda.synchronize()  # (the search runs on the library's stream)
+        got = idx.search(dq, 20, "nprobe=4", out=out, async_=True)
+        torch.cuda.synchronize()
+        mq.vector_scan.async_check()
+        assert got[0] is out[0] and got[1] is out[1]
+        assert_same(out[0].cpu().numpy(), out[1].cpu().numpy(), want_ids, dist, ctx)
+
+    run_async("async", ids)
+    m = (np.arange(n, dtype=np.uint64) * 7 + 3) % np.uint64(n)
+    idx.set_row_ids_map(m)
+    try:
+        run_async("async, row_ids_map", np.where(ids >= 0, m[np.maximum(ids, 0)].astype(np.int64), -1))
+    finally:
+        idx.set_row_ids_map(None)
+
+
+def test_binary_index_sub_batch_stats(mq, small):
+    """The stats of a sub-batched search are the sums over its sub-batches:
+    k_bivf_stats adds values, items, plane_bytes and pairs per (query, probe)
+    pair, so they equal the unbatched search's."""
+    from myscaledb_amd._lib import lib
+    idx, q = small["idx"], small["queries"]
+    idx.search(q, 20, "nprobe=39")
+    whole = mq.vector_index.last_index_stats()
+    prev = lib.mqvs_set_scratch_budget(1 << 20)  # 6 queries per sub-batch, as test_binary_index_query_sub_batches
+    try:
+        idx.search(q, 20, "nprobe=39")
+        st = mq.vector_index.last_index_stats()
+    finally:
+        lib.mqvs_set_scratch_budget(prev)
+    assert st["nq"] == len(q) and st["k"] == 20 and st["nprobe"] == 39
+    assert st["pairs"] == 39 * len(q)
+    for f in ("values", "items", "plane_bytes", "pairs"):
+        assert st[f] == whole[f], (f, st[f], whole[f])
+    assert st["values"] > 0 and st["plane_bytes"] > 0
+    assert st["rerank_ms"] == 0 and st["reranked"] == 0
+
+
 def test_binary_index_stats(mq, small):
     idx, q = small["idx"], small["queries"]
     idx.search(q, 20, "nprobe=4")

@@ -3,7 +3,7 @@
 
 The list scan (k_ivf_scan, kernels_ivf.hip) keeps a tile of 16 QB bf16
 queries in LDS: 16 QB (2 dpad + 16) bytes of dynamic LDS + 256 QB static.
-list_pass (index.hip) wants 64-query items when lists average >= 40 probing
+list_pass (index_search.hip) wants 64-query items when lists average >= 40 probing
 queries (E = nq nprobe >= 40 nlist), 32 from 24 and on every dense pass, 16
 otherwise, and takes the largest of that size and its smaller siblings that
 fits a workgroup's LDS (ivf_fit_qg): with 160 KiB, 64 up to dpad 1216, 32 up
