@@ -661,9 +661,10 @@ struct Error {
     } while (0)
 
 // ---------------------------------------------------------------------------
-// Host-side plumbing shared by the host files: mqvs.hip (the workspace gate,
-// host waits, segments, C ABI glue), search.hip and search_binary.hip
-// (the FLAT searches), index.hip (the index path)
+// Host-side plumbing shared by the host files: mqvs.hip (C ABI glue, modes),
+// workspace.hip (the workspace gate), wait.hip (host waits), segment.hip
+// (segments), search.hip and search_binary.hip (the FLAT searches), index.hip
+// (the index path)
 
 [[noreturn]] inline void fail(int code, const std::string &msg) { throw Error{code, msg}; }
 
@@ -785,7 +786,7 @@ static int guarded(F &&f) {
     }
 }
 
-// the stream of the calling thread's workspace on `device`
+// the stream of the calling thread's workspace on `device` (workspace.hip)
 hipStream_t thread_stream(int device);
 // compute units of the current device (cached per device: launchers size
 // their persistent grids from it on every call)
@@ -793,8 +794,8 @@ int device_cus();
 // LDS bytes one workgroup of the current device can have, static + dynamic
 // (hipDeviceAttributeMaxSharedMemoryPerBlock, read once per device)
 int64_t device_lds_bytes();
-// The host's wait for the work queued on `s` (every synchronous call ends with
-// one): the policy of mqvs_set_wait_mode -- the runtime's own
+// The host's wait for the work queued on `s` (wait.hip; every synchronous call
+// ends with one): the policy of mqvs_set_wait_mode -- the runtime's own
 // hipStreamSynchronize, or a short poll of a blocking-sync event's completion
 // followed by a blocking wait on it (the calling thread sleeps instead of
 // holding a core for the length of the search).  The current device must be
@@ -965,7 +966,7 @@ int wait_spin_us();
 // hyper-thread and saves power while polling)
 void cpu_relax();
 double measure_read_sweep(size_t bytes, int reps, hipStream_t s, double *best_ms);
-// Thread-local state of mqvs.hip: the stats of the thread's last search
+// What mqvs.hip keeps per thread and per process: the stats of the thread's last search
 // (mqvs_last_search_stats), and the per-call mode flags resolved against the
 // process-wide defaults (mqvs_set_*)
 mqvs_search_stats &search_stats();
@@ -984,6 +985,7 @@ void rerank_flat(mqvs_segment *seg, const float *queries, int nq, const int64_t 
                  const uint8_t *exists, int64_t *out_ids, float *out_dist, uint32_t flags, hipStream_t stream);
 void search_binary(mqvs_segment *seg, const uint8_t *queries, int nq, int k, int metric, const uint8_t *filter,
                    const uint8_t *exists, int64_t *out_ids, float *out_dist, uint32_t flags, hipStream_t stream);
+// segment.hip's services for the other paths:
 // rows of `nbytes` (host or device) -> zero-padded [n][words] on the device
 void upload_codes(uint32_t *dst, int words, const uint8_t *src, int64_t nbytes, int64_t n, bool dev, hipStream_t s);
 // segment from rows already on the current device (copied); granule = n

@@ -1,5 +1,5 @@
 // workspace.h -- the per-thread device workspace of the FLAT paths and the
-// process-wide gate on the HBM all workspaces hold (mqvs.hip).
+// process-wide gate on the HBM all workspaces hold (workspace.hip).
 #pragma once
 
 #include <mutex>
@@ -53,6 +53,8 @@ struct Workspace {
 
 // the calling thread's workspace on `device` (created on first use)
 Workspace &workspace(int device);
+// every workspace of the calling thread freed (mqvs_thread_release)
+void release_thread_workspaces();
 
 // one call of the owning thread on its workspace (nests): counted as running
 // and made the thread's current one for GBuf growth; at the end, if other
@@ -67,6 +69,15 @@ struct WsCall {
 
    private:
     Workspace *prev_;
+};
+
+// A call on the calling thread's workspace of the current device, on the
+// caller's stream or, when that is null, the workspace's own
+struct DeviceCall {
+    Workspace &ws;
+    WsCall call;
+    hipStream_t s;
+    explicit DeviceCall(hipStream_t stream);
 };
 
 // ASYNC searches cannot run the host-driven fallbacks (exact re-scan after a
