@@ -269,7 +269,7 @@ int mqvs_merge_shards(int32_t nshards, int32_t nq, int32_t k, int32_t metric,
  * the segments were not prepared for -> MQVS_ERR_LOGICAL.  The call honours
  * mqvs_inject_fault as mqvs_search does (outputs untouched) and its scratch
  * passes the workspace budget gate, counted in the thread's workspace.
- * Two routes, the same bits on both:
+ * Three routes, the same bits on all of them:
  *   fused     nq < 20, k <= 4096, and the part has its rows in HBM and at most
  *             the part-group row limit of them: all such parts are searched by
  *             one query prep, one grouped exact fp32 scan (dense values), one
@@ -281,16 +281,38 @@ int mqvs_merge_shards(int32_t nshards, int32_t nq, int32_t k, int32_t metric,
  *             stays 0).  Cosine: the query variant table is sized for the part
  *             with the most chunk ordinals (up to 16384, within the scratch
  *             budget), so a chain that does not repeat needs no second run.
- *   per part  every other part and call (nq >= 20, k > 4096, rows in host
- *             memory, larger parts; also a cosine part that carries a PREWHERE
- *             filter, whose chunk ordinals come from the filter, and a cosine
- *             part of more chunk ordinals than the variant table may hold):
- *             mqvs_search's own path on the same stream; the list joins the
- *             same merge.
+ *   fused     nq >= 20, off unless mqvs_set_part_group_batch has set a row
+ *   batch     limit: then k <= 4096, nq at most the setting's max_nq (when it
+ *             has one), and the part has its rows in HBM and at most the batch
+ *             row limit of them.  The same chain as the fused route -- one
+ *             query prep (with |q|^2 for L2), per slice of parts one grouped
+ *             scan and one grouped select, the merge, one host wait -- on the
+ *             exact fp32 MFMA scan of faiss's BLAS formula branch (128-row
+ *             tiles, the dense matrix [nq][rows] fp32 sliced by
+ *             mqvs_set_scratch_budget).  No overflow, no re-run (redo 0); the
+ *             cosine variant table is sized as on the fused route.
+ *   per part  every other part and call (k > 4096, rows in host memory,
+ *             larger parts, nq >= 20 with the batch route off or past its
+ *             max_nq; on both fused routes also a cosine part that carries a
+ *             PREWHERE filter, whose chunk ordinals come from the filter, and
+ *             a cosine part of more chunk ordinals than the variant table may
+ *             hold): mqvs_search's own path on the same stream; the list
+ *             joins the same merge.
  * mqvs_set_part_group_rows: the row limit of the fused route (default 131072,
  * the largest measured part size at which the fused route still beat the
  * per-part one at nq 1 and nq 16, profiles/part_group; at most 2^24); returns
- * the previous value, 0 leaves it unchanged. */
+ * the previous value, 0 leaves it unchanged.
+ * mqvs_set_part_group_batch: rows = 0 turns the fused batch route off (the
+ * default: every call then takes the routes, launches and stats it took
+ * before the route existed); 1 .. 2^24 is its row limit.  max_nq = 0: no cap
+ * on nq, else a cap >= 20.  Other values: MQVS_ERR_BAD_ARGUMENTS, nothing
+ * changed.  mqvs_part_group_batch reads the pair (either pointer may be NULL).
+ * Recommended when batches arrive over many small parts: (131072, 128), the
+ * largest measured pair at which the fused batch route beat the per-part one
+ * at every measured nq up to max_nq (20, 128), for L2 and cosine, in groups
+ * of 8 equal parts (profiles/part_group, "Batches"); at nq 1000 it wins for
+ * 64 parts of 8192 rows and 256 of 1000 but loses for 8 parts of 16384 or
+ * 32768 rows, where the per-part route's bf16 pre-filter is faster. */
 typedef struct mqvs_part_group *mqvs_part_group_t;
 int mqvs_part_group_create(const mqvs_segment_t *segs, int32_t nparts, mqvs_part_group_t *out);
 int mqvs_part_group_free(mqvs_part_group_t group);
@@ -312,10 +334,12 @@ typedef struct {
     int32_t redo;         /* fused parts re-run per part (always 0: see above) */
     int32_t nq;
     int32_t k;
-    int32_t reserved;
+    int32_t batch;        /* 1 when the call's fused parts ran the fused batch route (the MFMA scan) */
 } mqvs_part_group_stats;
 int mqvs_part_group_last_stats(mqvs_part_group_stats *out);
 int64_t mqvs_set_part_group_rows(int64_t rows);
+int mqvs_set_part_group_batch(int64_t rows, int32_t max_nq);
+int mqvs_part_group_batch(int64_t *rows, int32_t *max_nq);
 
 /* ---- column ingest: a part's Array(Float32) column from its compressed files
  * Replaces the per-granule host read + copy of vectorScanWithoutIndex

@@ -62,7 +62,7 @@ SYMBOLS = [
     "mqvs_cache_create", "mqvs_cache_free", "mqvs_cache_put", "mqvs_cache_acquire", "mqvs_cache_release",
     "mqvs_cache_remove", "mqvs_cache_stats", "mqvs_inject_fault", "mqvs_set_wait_mode",
     "mqvs_part_group_create", "mqvs_part_group_free", "mqvs_part_group_info", "mqvs_part_group_search",
-    "mqvs_part_group_last_stats", "mqvs_set_part_group_rows",
+    "mqvs_part_group_last_stats", "mqvs_set_part_group_rows", "mqvs_set_part_group_batch", "mqvs_part_group_batch",
 ]
 
 
@@ -85,7 +85,7 @@ class PartGroupStats(ctypes.Structure):
                 ("parts", ctypes.c_int32), ("fused_parts", ctypes.c_int32),
                 ("looped_parts", ctypes.c_int32), ("launches", ctypes.c_int32),
                 ("redo", ctypes.c_int32), ("nq", ctypes.c_int32), ("k", ctypes.c_int32),
-                ("reserved", ctypes.c_int32)]
+                ("batch", ctypes.c_int32)]
 
 
 class IndexInfo(ctypes.Structure):
@@ -223,6 +223,8 @@ def _load(path=LIB_PATH):
         "mqvs_part_group_search": ([P, P, I32, I32, I32, P, P, P, P, P, U32, P], ctypes.c_int),
         "mqvs_part_group_last_stats": ([P], ctypes.c_int),
         "mqvs_set_part_group_rows": ([I64], I64),
+        "mqvs_set_part_group_batch": ([I64, I32], ctypes.c_int),
+        "mqvs_part_group_batch": ([P, P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

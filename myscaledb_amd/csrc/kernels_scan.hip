@@ -320,20 +320,27 @@ void launch_scan_group(const ScanParams &base, const GroupSlot *slots, int nslot
 constexpr int MB_K = 32;          // K per stage
 constexpr int MB_LD = MB_K + 1;   // odd LDS row stride: conflict-free ds_read_b32 columns
 
-template <int METRIC, bool PROBE, bool VEC4>
-__global__ __launch_bounds__(256, 2) void k_scan_mfma(ScanParams p) {
-    __shared__ float Ys[2][kMfmaRows * MB_LD];
-    __shared__ float Qs[2][kMfmaQ * MB_LD];
-    // XCD-aware block -> (row tile, query block): the query blocks of one row
-    // tile are consecutive logical blocks and land on one XCD (same L2).
-    const int64_t L = p.tiles * p.num_qblocks;
+// XCD-aware block -> logical work item l of L = tiles x query blocks (false:
+// a block of the grid's round-up): the query blocks of one row tile are
+// consecutive logical items and land on one XCD (same L2).
+__device__ __forceinline__ bool mfma_block_item(int64_t tiles, int num_qblocks, int64_t &ti, int &qb) {
+    const int64_t L = tiles * num_qblocks;
     const int64_t cpx = (L + 7) / 8;
     const int64_t b = blockIdx.x;
     const int64_t l = (b % 8) * cpx + b / 8;
-    if (l >= L) return;
-    const int64_t ti = l / p.num_qblocks;
-    const int qb = (int)(l % p.num_qblocks);
+    if (l >= L) return false;
+    ti = l / num_qblocks;
+    qb = (int)(l % num_qblocks);
+    return true;
+}
 
+// One (row tile ti, query block qb) of the scan (the whole workgroup calls it
+// with the same ti and qb): the body k_scan_mfma and the part-group kernel
+// k_scan_group_mfma share, so both compute a row's value with the same
+// instructions.  Ys / Qs: the workgroup's LDS stages, free on entry.
+template <int METRIC, bool PROBE, bool VEC4>
+__device__ __forceinline__ void scan_mfma_tile(const ScanParams &p, int64_t ti, int qb, float (*Ys)[kMfmaRows * MB_LD],
+                                               float (*Qs)[kMfmaQ * MB_LD]) {
     int64_t r0, r1, chunk;
     tile_range(p, ti, r0, r1, chunk);
     if (r0 >= r1) return;  // tile past the end of a partial last granule
@@ -454,6 +461,80 @@ __global__ __launch_bounds__(256, 2) void k_scan_mfma(ScanParams p) {
     epi(acc01, 0, 1);
     epi(acc10, 1, 0);
     epi(acc11, 1, 1);
+}
+
+template <int METRIC, bool PROBE, bool VEC4>
+__global__ __launch_bounds__(256, 2) void k_scan_mfma(ScanParams p) {
+    __shared__ float Ys[2][kMfmaRows * MB_LD];
+    __shared__ float Qs[2][kMfmaQ * MB_LD];
+    int64_t ti;
+    int qb;
+    if (!mfma_block_item(p.tiles, p.num_qblocks, ti, qb)) return;
+    scan_mfma_tile<METRIC, PROBE, VEC4>(p, ti, qb, Ys, Qs);
+}
+
+// Part-group batch scan (part_group.hip): k_scan_mfma's PROBE work items over
+// many parts in one launch.  One (row tile, query block) per workgroup, so the
+// body's returns and barriers stay block-uniform; tile ti of the launch
+// belongs to the slot whose [tile0, next tile0) holds it, tiles counted in
+// kMfmaRows rows (slots[nslots] is the sentinel).  The workgroup takes that
+// part's fields into its ScanParams and runs the shared body, so a row's
+// value is the one mqvs_search's fp32 batch scan computes for it.
+template <int METRIC, bool VEC4>
+__global__ __launch_bounds__(256, 2) void k_scan_group_mfma(ScanParams p, const GroupSlot *slots, int nslots,
+                                                            int64_t tiles) {
+    __shared__ float Ys[2][kMfmaRows * MB_LD];
+    __shared__ float Qs[2][kMfmaQ * MB_LD];
+    int64_t ti;
+    int qb;
+    if (!mfma_block_item(tiles, p.num_qblocks, ti, qb)) return;
+    // the last slot with tile0 <= ti (slots without tiles are skipped)
+    int lo = 0, hi = nslots;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (slots[mid].tile0 <= ti) lo = mid;
+        else hi = mid;
+    }
+    const GroupSlot &g = slots[lo];
+    p.rows = g.rows;
+    p.row_norms = g.row_norms;
+    p.n = g.n;
+    p.chunk_rows = g.granule;
+    p.chunk_ord = g.chunk_ord;
+    p.ord_base = (int)(g.row_offset / g.granule);
+    p.filter = g.filter;
+    p.exists = g.exists;
+    p.nonempty = g.nonempty;
+    p.row_begin = 0;
+    p.row_end = g.n;
+    p.tiles_per_chunk = g.tiles_per_chunk;
+    p.tile_rows = kMfmaRows;
+    p.probe = p.probe + g.col0;
+    scan_mfma_tile<METRIC, true, VEC4>(p, ti - g.tile0, qb, Ys, Qs);
+}
+
+template <int METRIC>
+static void launch_group_mfma_t(const ScanParams &p, const GroupSlot *slots, int nslots, int64_t tiles,
+                                hipStream_t s) {
+    const int64_t L = tiles * p.num_qblocks;
+    const int64_t grid = (L + 7) / 8 * 8;
+    if (L < 1) return;
+    if (grid > 0x7FFFFFFF) fail(MQVS_ERR_BAD_ARGUMENTS, "part group batch scan: more work items than one launch holds");
+    if (p.d % 4 == 0)
+        hipLaunchKernelGGL((k_scan_group_mfma<METRIC, true>), dim3((unsigned)grid), dim3(256), 0, s, p, slots, nslots,
+                           tiles);
+    else
+        hipLaunchKernelGGL((k_scan_group_mfma<METRIC, false>), dim3((unsigned)grid), dim3(256), 0, s, p, slots,
+                           nslots, tiles);
+}
+
+void launch_scan_group_mfma(const ScanParams &base, const GroupSlot *slots, int nslots, int64_t tiles, int metric,
+                            hipStream_t s) {
+    switch (metric) {
+        case MQVS_METRIC_L2: launch_group_mfma_t<MQVS_METRIC_L2>(base, slots, nslots, tiles, s); break;
+        case MQVS_METRIC_IP: launch_group_mfma_t<MQVS_METRIC_IP>(base, slots, nslots, tiles, s); break;
+        default: launch_group_mfma_t<MQVS_METRIC_COSINE>(base, slots, nslots, tiles, s); break;
+    }
 }
 
 template <int METRIC, bool PROBE>

@@ -255,6 +255,7 @@ __device__ inline bool row_valid(const ScanParams &p, int64_t r) {
 // table of m slots ends with a sentinel whose tile0 is the launch's tile count.
 struct GroupSlot {
     const float *rows;
+    const float *row_norms;   // the segment's |y|^2 per row (batch scan, L2)
     const int *chunk_ord;     // as ScanParams::chunk_ord
     const uint8_t *nonempty;
     const uint8_t *filter;    // this call's PREWHERE bitmap of the part, or null
@@ -269,6 +270,10 @@ struct GroupSlot {
 // set; the per-part fields come from the slots
 void launch_scan_group(const ScanParams &base, const GroupSlot *slots, int nslots, int64_t tiles, int metric,
                        hipStream_t s);
+// the batch form (nq >= kBlasThreshold): k_scan_mfma's work items, tiles of
+// kMfmaRows rows; base also holds qnorms and num_qblocks
+void launch_scan_group_mfma(const ScanParams &base, const GroupSlot *slots, int nslots, int64_t tiles, int metric,
+                            hipStream_t s);
 // per (slot, query) the k best rows of the slice in mqvs_search's order ->
 // list_ids / list_dist [group parts][nq][k] at the slot's part
 void launch_select_group(const float *matrix, int64_t ld, const GroupSlot *slots, int nslots, int nq, int k,

@@ -11,6 +11,10 @@
 //   3. grouped select    k_select_group: k_final_select's body per (part,
 //                        query) over the part's slice -> per-part top-k lists
 //   4. merge             k_merge_shards (part merge) with the list index out
+// The batch route (nq >= 20, opted in by mqvs_set_part_group_batch) is the
+// same chain on the exact fp32 BLAS-branch scan: the query prep also produces
+// |q|^2 for L2, step 2 is k_scan_group_mfma (k_scan_mfma's PROBE work items,
+// 128-row tiles), steps 3 and 4 are unchanged.
 // Parts the fused route does not take run mqvs_search's own path on the same
 // stream into their list of the same merge.  Nothing here depends on what a
 // kernel found: the call has one host wait, after the merge.
@@ -38,6 +42,10 @@ constexpr int64_t kGroupRowsMax = (int64_t)1 << 24;  // a part's slice is indexe
 // to 131072 rows at nq 1 and nq 16, the per-part route (bf16 pre-filter, half
 // the bytes) from 262144 rows at nq 1 and from 524288 at nq 16
 static std::atomic<int64_t> g_group_rows{131072};
+// the batch route (mqvs_set_part_group_batch): row limit in the low 32 bits
+// (0 = off, the default), max_nq above them (0 = no cap) -- one word, so a
+// search reads a pair some call set
+static std::atomic<int64_t> g_group_batch{0};
 static thread_local mqvs_part_group_stats t_group_stats{};
 
 static bool rows_fusable(const mqvs_segment *s, int64_t limit) { return !s->rows_host && s->n <= limit; }
@@ -108,14 +116,21 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
     // ---- the routes.  Cosine: the variant table holds maxv variants per
     // query; a part of more chunk ordinals is fused only while the table
     // grown to them stays within the scratch budget (and kMaxVariantsCap)
-    const int64_t limit = g_group_rows.load(std::memory_order_relaxed);
+    // batch: the call's nq selects faiss's BLAS formula -- its fused route is
+    // the MFMA scan, and only when opted in
+    const bool batch = nq >= kBlasThreshold;
+    const int64_t batch_set = g_group_batch.load(std::memory_order_relaxed);
+    const int64_t batch_rows = batch_set & 0xFFFFFFFF, batch_max_nq = batch_set >> 32;
+    const bool route_on = !batch || (batch_rows > 0 && (batch_max_nq == 0 || nq <= batch_max_nq));
+    const int64_t limit = batch ? batch_rows : g_group_rows.load(std::memory_order_relaxed);
+    const int64_t tile_rows = batch ? kMfmaRows : kSmallRows;
     const int64_t maxv_fit =
         std::min<int64_t>(kMaxVariantsCap, (int64_t)(scratch_budget() / (sizeof(float) * (size_t)nq * qstride)));
     std::vector<char> fused(nparts, 0);
     int nfused = 0, maxv = cos ? kMaxVariants : 1;
     for (int p = 0; p < nparts; ++p) {
         const mqvs_segment *seg = g->segs[p];
-        bool f = nq < kBlasThreshold && k <= kSortCap && rows_fusable(seg, limit);
+        bool f = route_on && k <= kSortCap && rows_fusable(seg, limit);
         if (f && cos) {
             if (filters && filters[p]) f = false;  // (its chunk ordinals come from the filter)
             const int64_t o = part_ords(seg);
@@ -128,6 +143,7 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
     }
     st.fused_parts = nfused;
     st.looped_parts = nparts - nfused;
+    st.batch = batch && nfused > 0;
 
     // ---- inputs.  Host bitmaps: every part's into one pinned buffer behind
     // the slot tables, one copy to the device
@@ -166,6 +182,7 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
             if (cur.nslots > 0 && cur.cols + seg->n > max_cols) close();
             GroupSlot e{};
             e.rows = seg->rows;
+            e.row_norms = seg->norms;
             e.chunk_ord = seg->chunk_ord;
             e.nonempty = seg->nonempty_bits;
             e.n = seg->n;
@@ -176,10 +193,10 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
             e.part = p;
             // cosine and chunk-ordinal parts: tiles that never span two chunks
             const bool aligned = cos || seg->chunk_ord != nullptr;
-            int64_t tiles = (seg->n + kSmallRows - 1) / kSmallRows;
+            int64_t tiles = (seg->n + tile_rows - 1) / tile_rows;
             if (aligned && seg->n > 0) {
                 // (a part shorter than its granule is one chunk: no tiles past its rows)
-                e.tiles_per_chunk = (std::min(seg->granule, seg->n) + kSmallRows - 1) / kSmallRows;
+                e.tiles_per_chunk = (std::min(seg->granule, seg->n) + tile_rows - 1) / tile_rows;
                 tiles = (seg->n + seg->granule - 1) / seg->granule * e.tiles_per_chunk;
             }
             slots.push_back(e);
@@ -237,8 +254,8 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
         float *qvars = (float *)ws.pg_qvars.get(sizeof(float) * (size_t)nq * maxv * qstride);
         // (a chain that does not repeat within maxv steps sets fl[4]: every
         // fused part has at most maxv chunk ordinals, so none reads past it)
-        launch_query_prep(dq, nq, d, cos ? MQVS_METRIC_COSINE : MQVS_METRIC_L2, false, qvars, maxv, qnorms, qmu, qlam,
-                          fl + 4, s);
+        launch_query_prep(dq, nq, d, cos ? MQVS_METRIC_COSINE : MQVS_METRIC_L2, batch && metric == MQVS_METRIC_L2, qvars,
+                          maxv, qnorms, qmu, qlam, fl + 4, s);
         MQVS_HIP(hipGetLastError());
         st.launches += 2;
         int64_t ld = 0;
@@ -253,11 +270,15 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
         p.qlam = qlam;
         p.maxv = maxv;
         p.blas_nq = nq;
+        p.num_qblocks = (nq + kMfmaQ - 1) / kMfmaQ;
         p.probe = matrix;
         for (const Slice &sl : slices) {
             p.probe_ld = sl.cols;
             if (sl.tiles > 0) {
-                launch_scan_group(p, dslots + sl.first_slot, sl.nslots, sl.tiles, metric, s);
+                if (batch)
+                    launch_scan_group_mfma(p, dslots + sl.first_slot, sl.nslots, sl.tiles, metric, s);
+                else
+                    launch_scan_group(p, dslots + sl.first_slot, sl.nslots, sl.tiles, metric, s);
                 MQVS_HIP(hipGetLastError());
                 st.launches += 1;
             }
@@ -346,6 +367,20 @@ int mqvs_part_group_search(mqvs_part_group_t group, const float *queries, int32_
 int mqvs_part_group_last_stats(mqvs_part_group_stats *out) {
     if (!out) return MQVS_ERR_BAD_ARGUMENTS;
     *out = t_group_stats;
+    return MQVS_OK;
+}
+
+int mqvs_set_part_group_batch(int64_t rows, int32_t max_nq) {
+    if (rows < 0 || rows > kGroupRowsMax || max_nq < 0 || (max_nq > 0 && max_nq < kBlasThreshold))
+        return MQVS_ERR_BAD_ARGUMENTS;
+    g_group_batch.store(rows | ((int64_t)max_nq << 32), std::memory_order_relaxed);
+    return MQVS_OK;
+}
+
+int mqvs_part_group_batch(int64_t *rows, int32_t *max_nq) {
+    const int64_t v = g_group_batch.load(std::memory_order_relaxed);
+    if (rows) *rows = v & 0xFFFFFFFF;
+    if (max_nq) *max_nq = (int32_t)(v >> 32);
     return MQVS_OK;
 }
 

@@ -24,11 +24,26 @@ def set_part_group_rows(rows: int) -> int:
     return int(lib.mqvs_set_part_group_rows(int(rows)))
 
 
+def set_part_group_batch(rows: int, max_nq: int = 0) -> None:
+    """The fused batch route (mqvs_set_part_group_batch): calls of nq >= 20
+    fuse the parts of at most ``rows`` rows on the fp32 MFMA scan; ``rows`` 0
+    turns it off (the default).  ``max_nq`` 0: no cap, else calls of more
+    queries take the per-part route."""
+    check(lib.mqvs_set_part_group_batch(int(rows), int(max_nq)))
+
+
+def part_group_batch():
+    """(rows, max_nq) of the fused batch route; rows 0 = off."""
+    rows, max_nq = ctypes.c_int64(), ctypes.c_int32()
+    check(lib.mqvs_part_group_batch(ctypes.byref(rows), ctypes.byref(max_nq)))
+    return rows.value, max_nq.value
+
+
 def last_stats():
     """mqvs_part_group_last_stats of the calling thread as a dict."""
     st = _lib.PartGroupStats()
     check(lib.mqvs_part_group_last_stats(ctypes.byref(st)))
-    return {f: getattr(st, f) for f, _ in _lib.PartGroupStats._fields_ if f != "reserved"}
+    return {f: getattr(st, f) for f, _ in _lib.PartGroupStats._fields_}
 
 
 class PartGroup:

@@ -15,6 +15,19 @@ bit.  --limit-sweep times groups of 8 equal parts with the fused route on and
 off, per part size: where the per-part route becomes faster is where the
 default of mqvs_set_part_group_rows belongs.
 
+--batch is the same method for batches (nq >= 20; default nq 20, 128, 1000)
+and the fused batch route (mqvs_set_part_group_batch), device arrays
+throughout:
+  b      as above
+  c_off  mqvs_part_group_search with the batch route off: every part looped
+         inside the call
+  c_on   the same call with the batch route on
+a runs once, untimed, and the outputs of c_off and c_on must equal it bit for
+bit.  Each record carries, per variant, the spread of the three block medians
+and whether c_on wins against b and against c_off: its median is below the
+other's by more than both spreads.  With --batch, --limit-sweep times c_on
+against c_off for groups of 8 equal parts per part size and nq.
+
 One JSON line per measurement on stdout (and --out)."""
 import argparse
 import ctypes
@@ -119,9 +132,76 @@ def time_variants(run, variants, warmup, rounds):
     for v, x in t.items():
         b = max(1, len(x) // 3)
         blocks = [statistics.median(x[i:i + b]) for i in range(0, b * 3, b) if x[i:i + b]]
-        out[v] = dict(median_ms=statistics.median(x), block_medians_ms=blocks, min_ms=min(x), max_ms=max(x),
-                      rounds=len(x))
+        out[v] = dict(median_ms=statistics.median(x), block_medians_ms=blocks, spread_ms=max(blocks) - min(blocks),
+                      min_ms=min(x), max_ms=max(x), rounds=len(x))
     return out
+
+
+def wins(res, v, other):
+    """v's median is below other's by more than both variants' spread"""
+    return bool(res[other]["median_ms"] - res[v]["median_ms"] > max(res[v]["spread_ms"], res[other]["spread_ms"]))
+
+
+def batch_mode(args, mq, emit):
+    """--batch: b, c_off and c_on per case, then the limit sweep (c_on against c_off)"""
+    from myscaledb_amd.part_group import last_stats, part_group_batch, set_part_group_batch
+    prev = part_group_batch()
+    nqs = [int(x) for x in (args.nqs if args.nqs != "1,16" else "20,128,1000").split(",")]
+
+    def runner(tb):
+        def run(v):
+            if v in ("c_off", "c_on"):
+                set_part_group_batch((1 << 24) if v == "c_on" else 0)
+                tb.run("c_dev")
+            else:
+                tb.run(v)
+        return run
+
+    def same_as_a(tb, run):
+        run("a")
+        ia, da = tb.results("a")
+        same, stats = {}, {}
+        for v in ("c_off", "c_on"):
+            run(v)
+            iv, dv = tb.results("c_dev")
+            same[v] = bool(np.array_equal(ia, iv) and np.array_equal(da.view(np.uint32), dv.view(np.uint32)))
+            stats[v] = last_stats()
+        return same, stats
+
+    try:
+        for case in [c for c in args.cases.split(",") if c]:
+            nparts, rows = (int(x) for x in case.split("x"))
+            for metric in args.metrics.split(","):
+                for nq in nqs:
+                    tb = Table(mq, nparts, rows, args.dim, metric, nq, args.k)
+                    try:
+                        run = runner(tb)
+                        res = time_variants(run, ["b", "c_off", "c_on"], args.warmup, args.rounds)
+                        same, stats = same_as_a(tb, run)
+                        emit(dict(kind="batch_case", parts=nparts, rows=rows, d=args.dim, nq=nq, k=args.k,
+                                  metric=metric, times=res, equals_a=same, group_stats=stats,
+                                  c_on_wins=dict(b=wins(res, "c_on", "b"), c_off=wins(res, "c_on", "c_off"))))
+                        if not all(same.values()):
+                            raise SystemExit(f"outputs differ from variant a: {same}")
+                    finally:
+                        tb.free()
+        for rows in [int(x) for x in args.limit_sweep.split(",") if x]:
+            for metric in args.metrics.split(","):
+                for nq in nqs:
+                    tb = Table(mq, 8, rows, args.dim, metric, nq, args.k)
+                    try:
+                        run = runner(tb)
+                        res = time_variants(run, ["c_off", "c_on"], args.warmup, args.rounds)
+                        same, stats = same_as_a(tb, run)
+                        emit(dict(kind="batch_limit", parts=8, rows=rows, d=args.dim, nq=nq, k=args.k, metric=metric,
+                                  times=res, equals_a=same, group_stats=stats,
+                                  c_on_wins=dict(c_off=wins(res, "c_on", "c_off"))))
+                        if not all(same.values()):
+                            raise SystemExit(f"outputs differ from variant a: {same}")
+                    finally:
+                        tb.free()
+    finally:
+        set_part_group_batch(*prev)
 
 
 def main():
@@ -135,6 +215,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=33)
     ap.add_argument("--variants", default="a,b,c_host,c_dev")
     ap.add_argument("--limit-sweep", default="", help="part sizes ROWS,... of the row-limit sweep (8 parts each)")
+    ap.add_argument("--batch", action="store_true", help="the batch route: b, c_off, c_on at nq >= 20 (see above)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
 
@@ -149,6 +230,12 @@ def main():
         if sink:
             sink.write(line + "\n")
             sink.flush()
+
+    if args.batch:
+        batch_mode(args, mq, emit)
+        if sink:
+            sink.close()
+        return
 
     variants = [v for v in args.variants.split(",") if v]
     for case in [c for c in args.cases.split(",") if c]:
