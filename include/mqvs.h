@@ -254,10 +254,15 @@ int mqvs_merge_shards(int32_t nshards, int32_t nq, int32_t k, int32_t metric,
  * its rows between HBM and host memory (mqvs_segment_set_rows_host) while a
  * group holds it, and the group itself holds no device memory (hbm_bytes 0).
  * Errors of mqvs_part_group_create: nparts < 1, a null handle, or segments on
- * different devices -> MQVS_ERR_BAD_ARGUMENTS; a binary segment, differing
- * dimensions, or cosine and non-cosine segments mixed -> MQVS_ERR_LOGICAL.
- * mqvs_part_group_info: rows = the sum of the parts' rows; fusable_parts = the
- * parts whose rows are in HBM and number at most the part-group row limit.
+ * different devices -> MQVS_ERR_BAD_ARGUMENTS; binary and Float32 segments
+ * mixed, differing dimensions (binary: differing dim_bits), or cosine and
+ * non-cosine Float32 segments mixed -> MQVS_ERR_LOGICAL.  A group whose
+ * segments are all binary (FixedString) is searched by
+ * mqvs_part_group_search_binary, below; mqvs_part_group_search on it is
+ * MQVS_ERR_LOGICAL.
+ * mqvs_part_group_info: rows = the sum of the parts' rows; d = the dimension
+ * (binary: dim_bits); fusable_parts = the parts whose rows are in HBM and
+ * number at most the part-group row limit (binary: the binary row limit).
  *
  * mqvs_part_group_search.  filters / row_exists: host arrays of nparts
  * pointers; either array may be NULL, any entry may be NULL; each bitmap
@@ -312,7 +317,48 @@ int mqvs_merge_shards(int32_t nshards, int32_t nq, int32_t k, int32_t metric,
  * at every measured nq up to max_nq (20, 128), for L2 and cosine, in groups
  * of 8 equal parts (profiles/part_group, "Batches"); at nq 1000 it wins for
  * 64 parts of 8192 rows and 256 of 1000 but loses for 8 parts of 16384 or
- * 32768 rows, where the per-part route's bf16 pre-filter is faster. */
+ * 32768 rows, where the per-part route's bf16 pre-filter is faster.
+ *
+ * Binary part groups.  A group of binary segments (all of one dim_bits, on one
+ * device; a segment's default metric does not matter, a binary segment serves
+ * Hamming and Jaccard) holds the parts of a FixedString(N) column that have no
+ * BINARYMSTG index yet.  mqvs_part_group_search_binary returns, for every
+ * input, exactly what
+ *     mqvs_search_binary(segs[p], queries, nq, k, metric, filters[p],
+ *         row_exists[p]) for every p, then
+ *     mqvs_merge_shards(nparts, ..., MQVS_F_PART_MERGE) over the lists in
+ *         group order
+ * returns: ids (row_offset + row), distance bits and order (ascending by
+ * distance, then part, then position in the part's list) match bit for bit;
+ * padding slots hold id -1 and FLT_MAX, and out_part the group position of
+ * each result, -1 in padding slots.  queries: nq x dim_bits / 8 bytes.  The
+ * bitmaps, the pointer arrays, MQVS_F_DEVICE_PTRS and MQVS_F_ASYNC (ignored:
+ * one host wait, after the merge) are as in mqvs_part_group_search; so are
+ * the nparts * k limit, mqvs_inject_fault, the workspace gate and the stats
+ * (mqvs_part_group_last_stats, batch = 0).  A metric other than Hamming /
+ * Jaccard -> MQVS_ERR_NOT_IMPLEMENTED; the call on a Float32 group ->
+ * MQVS_ERR_LOGICAL.
+ * Two routes, the same bits on both:
+ *   fused     k <= 4096 and the part has its codes in HBM and at most the
+ *             binary row limit of them, at any nq (binary distances have no
+ *             formula switch at nq 20): the query codes are uploaded once,
+ *             then per slice of parts (the dense [nq][rows] fp32 matrix cut by
+ *             mqvs_set_scratch_budget) one grouped popcount scan -- the dense
+ *             values of mqvs_search_binary's own scans: the Hamming count, the
+ *             fp32 Jaccard (den - num) / den, NaN for a row that is filtered,
+ *             deleted or at Hamming distance dim_bits -- and one grouped
+ *             select, then the merge.  Every row of a part is a candidate of
+ *             its select: nothing overflows, redo stays 0.  A filter never
+ *             sends a part to the other route (no chunk ordinals here).
+ *   per part  everything else (k > 4096, larger parts): mqvs_search_binary's
+ *             own path on the same stream; the list joins the same merge.
+ * mqvs_set_part_group_binary_rows: the binary row limit (default 131072, the
+ * largest measured part size at which the fused route beat the per-part one
+ * at nq 1, 16 and 128 for both metrics, profiles/part_group/binary_limit.jsonl
+ * -- up to 32768 rows mqvs_search_binary itself scans the whole part into
+ * dense values, so there the fused route does the same device work with fewer
+ * launches and waits; at most 2^24); returns the previous value, 0 leaves it
+ * unchanged. */
 typedef struct mqvs_part_group *mqvs_part_group_t;
 int mqvs_part_group_create(const mqvs_segment_t *segs, int32_t nparts, mqvs_part_group_t *out);
 int mqvs_part_group_free(mqvs_part_group_t group);
@@ -322,7 +368,11 @@ int mqvs_part_group_search(mqvs_part_group_t group, const float *queries, int32_
                            const uint8_t *const *filters, const uint8_t *const *row_exists,
                            int32_t *out_part, int64_t *out_ids, float *out_dist,
                            uint32_t flags, mqvs_stream_t stream);
-/* Stats of the calling thread's last mqvs_part_group_search. */
+int mqvs_part_group_search_binary(mqvs_part_group_t group, const uint8_t *queries, int32_t nq, int32_t k,
+                                  int32_t metric, const uint8_t *const *filters, const uint8_t *const *row_exists,
+                                  int32_t *out_part, int64_t *out_ids, float *out_dist,
+                                  uint32_t flags, mqvs_stream_t stream);
+/* Stats of the calling thread's last mqvs_part_group_search / _search_binary. */
 typedef struct {
     double total_ms;      /* host time of the call (only with mqvs_set_timing(1) or MQVS_F_TIMING) */
     int64_t fused_rows;   /* rows of the fused parts */
@@ -338,6 +388,7 @@ typedef struct {
 } mqvs_part_group_stats;
 int mqvs_part_group_last_stats(mqvs_part_group_stats *out);
 int64_t mqvs_set_part_group_rows(int64_t rows);
+int64_t mqvs_set_part_group_binary_rows(int64_t rows);
 int mqvs_set_part_group_batch(int64_t rows, int32_t max_nq);
 int mqvs_part_group_batch(int64_t *rows, int32_t *max_nq);
 

@@ -988,4 +988,85 @@ private:
     int metric = 0;
 };
 
+/// The same over the parts of a FixedString(N) column that have no BINARYMSTG
+/// index yet (mqvs_part_group_search_binary): the per-part
+/// BinaryPartScan::search calls and mergePartResults in one launch chain and
+/// one host wait.  The parts share one code width; a search names Hamming or
+/// Jaccard, whatever the parts' default metric.
+class BinaryPartGroup
+{
+public:
+    explicit BinaryPartGroup(const std::vector<const BinaryPartScan *> & parts)
+    {
+        std::vector<mqvs_segment_t> segs;
+        for (const BinaryPartScan * p : parts)
+            segs.push_back(p ? p->handle() : nullptr);
+        mqvs_part_group_t g = nullptr;
+        check(mqvs_part_group_create(segs.data(), static_cast<int32_t>(segs.size()), &g));
+        group = std::make_shared<GroupHandle>(g, true);
+        nparts = static_cast<int32_t>(segs.size());
+        code_bytes = parts[0]->codeBytes();
+    }
+
+    int32_t parts() const { return nparts; }
+    int32_t codeBytes() const { return code_bytes; }
+    mqvs_part_group_t handle() const { return group->h; }
+
+    /// The CPU path the call replaces: the part scans and the cross-part merge,
+    /// same arguments and outputs.
+    using GroupFallback = std::function<void(const uint8_t * queries, int32_t nq, int32_t k, int mqvs_metric,
+                                             const uint8_t * const * filters, const uint8_t * const * row_exists,
+                                             int32_t * part, int64_t * ids, float * dist)>;
+
+    /// Raw merged top-k: part / ids / dist nq*k (caller-owned), ascending by
+    /// (distance, part, position); padding slots hold part -1, id -1, FLT_MAX.
+    /// queries: nq codes of codeBytes() bytes.  filters / row_exists: nparts
+    /// bitmap pointers (either array, and any entry, may be nullptr).
+    /// fallback: runs instead when the device fails (isFallbackStatus).
+    void search(const uint8_t * queries, int32_t nq, int32_t k, int mqvs_metric, const uint8_t * const * filters,
+                const uint8_t * const * row_exists, int32_t * part, int64_t * ids, float * dist, uint32_t flags = 0,
+                const GroupFallback & fallback = nullptr) const
+    {
+        const int st = mqvs_part_group_search_binary(group->h, queries, nq, k, mqvs_metric, filters, row_exists, part,
+                                                     ids, dist, flags, nullptr);
+        checkOrFallback(st, static_cast<bool>(fallback),
+                        [&] { fallback(queries, nq, k, mqvs_metric, filters, row_exists, part, ids, dist); });
+    }
+
+    /// The labelled rows of the merged result, after the reference's check of
+    /// the query's FixedString length.
+    PartRows search(const uint8_t * queries, int32_t nq, int32_t query_bytes, int32_t k, int mqvs_metric,
+                    const uint8_t * const * filters = nullptr, const uint8_t * const * row_exists = nullptr,
+                    const GroupFallback & fallback = nullptr) const
+    {
+        if (query_bytes != code_bytes)
+            throw DB::Exception(DB::ErrorCodes::LOGICAL_ERROR, "{}",
+                                std::string("The dimension of searched index and input doesn't match."));
+        std::vector<int32_t> part(static_cast<size_t>(nq) * k);
+        std::vector<int64_t> ids(part.size());
+        std::vector<float> dist(part.size());
+        search(queries, nq, k, mqvs_metric, filters, row_exists, part.data(), ids.data(), dist.data(), 0, fallback);
+        PartRows out;
+        for (size_t i = 0; i < ids.size(); ++i)
+        {
+            if (ids[i] <= -1)
+                continue;
+            out.part.push_back(static_cast<uint32_t>(part[i]));
+            out.label.push_back(static_cast<uint32_t>(ids[i]));
+            out.vector_id.push_back(static_cast<uint32_t>(i / static_cast<size_t>(k)));
+            out.distance.push_back(dist[i]);
+        }
+        return out;
+    }
+
+    /// The calling thread's last search (mqvs_part_group_last_stats).
+    static mqvs_part_group_stats lastStats() { return PartGroup::lastStats(); }
+
+private:
+    using GroupHandle = Handle<mqvs_part_group_t, mqvs_part_group_free>;
+    std::shared_ptr<GroupHandle> group;
+    int32_t nparts = 0;
+    int32_t code_bytes = 0;
+};
+
 }

@@ -32,6 +32,95 @@
 
 namespace mqvs {
 
+constexpr int kBinQC = 8;   // queries per pass (accumulators in registers)
+constexpr int kBinRW = 8;   // 16-B slices kept in registers (REG: rows <= 1024 bits)
+
+// ---------------------------------------------------------------------------
+// A row's value has one definition: bin_popc and bin_probe_value are the
+// expressions of every binary scan, the per-part kernels below and the grouped
+// ones (k_scan_group_binary*).  The loop shells around them (bin_load_row,
+// bin_row_pass, bin_co_popc) serve the grouped kernels only: they repeat the
+// shells of k_scan_binary / k_scan_binary_co, which keep theirs in place --
+// calling these from them changed their instruction streams (the REG form by
+// some 280 instructions), calling the two value functions did not.
+
+// one 16-B slice of a row against the same slice of a query
+template <int METRIC>
+__device__ __forceinline__ void bin_popc(const uint4 q, const uint4 y, uint32_t &a, uint32_t &b) {
+    if (METRIC == MQVS_METRIC_HAMMING) {
+        a += __builtin_popcount(q.x ^ y.x) + __builtin_popcount(q.y ^ y.y) +
+             __builtin_popcount(q.z ^ y.z) + __builtin_popcount(q.w ^ y.w);
+    } else {
+        a += __builtin_popcount(q.x & y.x) + __builtin_popcount(q.y & y.y) +
+             __builtin_popcount(q.z & y.z) + __builtin_popcount(q.w & y.w);
+        b += __builtin_popcount(q.x | y.x) + __builtin_popcount(q.y | y.y) +
+             __builtin_popcount(q.z | y.z) + __builtin_popcount(q.w | y.w);
+    }
+}
+
+// the dense PROBE value of a row: its distance, NaN when the row is not valid
+// (or, Hamming, at distance nbits)
+template <int METRIC>
+__device__ __forceinline__ float bin_probe_value(uint32_t a, uint32_t b, bool valid_row, int nbits) {
+    float raw;
+    bool valid = valid_row;
+    if (METRIC == MQVS_METRIC_HAMMING) {
+        raw = (float)a;
+        valid = valid && (int)a < nbits;
+    } else {
+        raw = a == 0u ? 1.0f : (float)(b - a) / (float)b;
+    }
+    return valid ? raw : __builtin_nanf("");
+}
+
+// row-per-lane form (k_scan_binary's load_row): the lane's row (position pos
+// of a tile ending at r1) into registers, zeros past the tile
+__device__ __forceinline__ void bin_load_row(const uint32_t *codes, int code_words, int W4, int64_t pos, int64_t r1,
+                                             uint4 (&dst)[kBinRW]) {
+    const uint4 *src = reinterpret_cast<const uint4 *>(codes + (pos < r1 ? pos : 0) * code_words);
+#pragma unroll
+    for (int u = 0; u < kBinRW; ++u) dst[u] = (u < W4 && pos < r1) ? src[u] : make_uint4(0u, 0u, 0u, 0u);
+}
+
+// row-per-lane form (k_scan_binary's query pass): the popcounts of kBinQC
+// queries from j0 over the lane's row (REG: yc, else read from yr)
+template <int METRIC, bool REG>
+__device__ __forceinline__ void bin_row_pass(const ScanParams &p, int j0, int W4, const uint4 (&yc)[kBinRW],
+                                             const uint4 *yr, bool inrange, uint32_t (&a)[kBinQC],
+                                             uint32_t (&b)[kBinQC]) {
+#pragma unroll
+    for (int jj = 0; jj < kBinQC; ++jj) a[jj] = b[jj] = 0u;
+    auto step = [&](const uint4 y, int u) {
+#pragma unroll
+        for (int jj = 0; jj < kBinQC; ++jj) {
+            if (j0 + jj < p.nq) {  // wave-uniform
+                const uint4 q = reinterpret_cast<const uint4 *>(p.qcodes + (int64_t)(j0 + jj) * p.code_words)[u];
+                bin_popc<METRIC>(q, y, a[jj], b[jj]);
+            }
+        }
+    };
+    if (REG) {
+#pragma unroll
+        for (int u = 0; u < kBinRW; ++u)
+            if (u < W4) step(yc[u], u);
+    } else {
+        for (int u = 0; u < W4; ++u) step(inrange ? yr[u] : make_uint4(0u, 0u, 0u, 0u), u);
+    }
+}
+
+// coalesced form (k_scan_binary_co): slice yy of a row against query slice q,
+// summed over the W4 lanes of the row
+template <int METRIC, int W4>
+__device__ __forceinline__ void bin_co_popc(const uint4 q, const uint4 yy, uint32_t &a, uint32_t &b) {
+    a = b = 0u;
+    bin_popc<METRIC>(q, yy, a, b);
+#pragma unroll
+    for (int o = 1; o < W4; o <<= 1) {
+        a += __shfl_xor(a, o);
+        if (METRIC == MQVS_METRIC_JACCARD) b += __shfl_xor(b, o);
+    }
+}
+
 template <int METRIC, bool PROBE, bool REG>
 __global__ __launch_bounds__(256) void k_scan_binary(ScanParams p) {
     constexpr int QC = 8;   // queries per pass (accumulators in registers)
@@ -74,15 +163,7 @@ __global__ __launch_bounds__(256) void k_scan_binary(ScanParams p) {
                 for (int jj = 0; jj < QC; ++jj) {
                     if (j0 + jj < p.nq) {  // wave-uniform
                         const uint4 q = reinterpret_cast<const uint4 *>(p.qcodes + (int64_t)(j0 + jj) * p.code_words)[u];
-                        if (METRIC == MQVS_METRIC_HAMMING) {
-                            a[jj] += __builtin_popcount(q.x ^ y.x) + __builtin_popcount(q.y ^ y.y) +
-                                     __builtin_popcount(q.z ^ y.z) + __builtin_popcount(q.w ^ y.w);
-                        } else {
-                            a[jj] += __builtin_popcount(q.x & y.x) + __builtin_popcount(q.y & y.y) +
-                                     __builtin_popcount(q.z & y.z) + __builtin_popcount(q.w & y.w);
-                            b[jj] += __builtin_popcount(q.x | y.x) + __builtin_popcount(q.y | y.y) +
-                                     __builtin_popcount(q.z | y.z) + __builtin_popcount(q.w | y.w);
-                        }
+                        bin_popc<METRIC>(q, y, a[jj], b[jj]);
                     }
                 }
             };
@@ -98,15 +179,8 @@ __global__ __launch_bounds__(256) void k_scan_binary(ScanParams p) {
                 const int j = j0 + jj;
                 if (j >= p.nq) break;  // wave-uniform
                 if (PROBE) {
-                    float raw;
-                    bool valid = valid_row;
-                    if (METRIC == MQVS_METRIC_HAMMING) {
-                        raw = (float)a[jj];
-                        valid = valid && (int)a[jj] < nbits;
-                    } else {
-                        raw = a[jj] == 0u ? 1.0f : (float)(b[jj] - a[jj]) / (float)b[jj];
-                    }
-                    if (inrange) p.probe[(int64_t)j * p.probe_ld + (pos - p.row_begin)] = valid ? raw : __builtin_nanf("");
+                    const float v = bin_probe_value<METRIC>(a[jj], b[jj], valid_row, nbits);
+                    if (inrange) p.probe[(int64_t)j * p.probe_ld + (pos - p.row_begin)] = v;
                     continue;
                 }
                 // APPEND: the threshold as a value (wave-uniform); keys of the
@@ -208,16 +282,8 @@ __global__ __launch_bounds__(256) void k_scan_binary_co(ScanParams p) {
             for (int jj = 0; jj < QC; ++jj) {
                 if (jj >= p.nq) break;  // wave-uniform
                 const uint4 q = qv[jj], yy = y[sidx];
-                uint32_t a, b = 0u;
-                if (METRIC == MQVS_METRIC_HAMMING) {
-                    a = __builtin_popcount(q.x ^ yy.x) + __builtin_popcount(q.y ^ yy.y) +
-                        __builtin_popcount(q.z ^ yy.z) + __builtin_popcount(q.w ^ yy.w);
-                } else {
-                    a = __builtin_popcount(q.x & yy.x) + __builtin_popcount(q.y & yy.y) +
-                        __builtin_popcount(q.z & yy.z) + __builtin_popcount(q.w & yy.w);
-                    b = __builtin_popcount(q.x | yy.x) + __builtin_popcount(q.y | yy.y) +
-                        __builtin_popcount(q.z | yy.z) + __builtin_popcount(q.w | yy.w);
-                }
+                uint32_t a = 0u, b = 0u;
+                bin_popc<METRIC>(q, yy, a, b);
 #pragma unroll
                 for (int o = 1; o < W4; o <<= 1) {
                     a += __shfl_xor(a, o);
@@ -225,15 +291,8 @@ __global__ __launch_bounds__(256) void k_scan_binary_co(ScanParams p) {
                 }
                 if (PROBE) {
                     if (lead && inrange) {
-                        float raw;
-                        bool valid = valid_row;
-                        if (METRIC == MQVS_METRIC_HAMMING) {
-                            raw = (float)a;
-                            valid = valid && (int)a < nbits;
-                        } else {
-                            raw = a == 0u ? 1.0f : (float)(b - a) / (float)b;
-                        }
-                        p.probe[(int64_t)jj * p.probe_ld + (row - p.row_begin)] = valid ? raw : __builtin_nanf("");
+                        p.probe[(int64_t)jj * p.probe_ld + (row - p.row_begin)] =
+                            bin_probe_value<METRIC>(a, b, valid_row, nbits);
                     }
                     continue;
                 }
@@ -304,6 +363,173 @@ void launch_scan_binary(const ScanParams &p, int metric, bool probe, hipStream_t
         probe ? scan_binary_t<MQVS_METRIC_HAMMING, true>(p, s) : scan_binary_t<MQVS_METRIC_HAMMING, false>(p, s);
     else
         probe ? scan_binary_t<MQVS_METRIC_JACCARD, true>(p, s) : scan_binary_t<MQVS_METRIC_JACCARD, false>(p, s);
+}
+
+// ---------------------------------------------------------------------------
+// Part-group scan (part_group.hip, mqvs_part_group_search_binary): the PROBE
+// form of the two scans above over many small parts in one launch, built as
+// k_scan_group is from k_scan_small.  Tile ti of the launch belongs to the
+// last slot with tile0 <= ti (slots[nslots] is the sentinel; slots without
+// tiles are skipped); the workgroup takes that part's fields into its
+// ScanParams and writes the part's dense values into columns [col0, col0 + n)
+// of the launch's [nq][probe_ld] matrix.  The code width is the group's, so
+// the form (coalesced / row per lane) holds across parts.  Binary parts need
+// no chunk-aligned tiling (no per-chunk arithmetic): tiles of kSmallRows rows
+// from row 0.
+__device__ __forceinline__ const GroupSlot &bin_group_slot(const GroupSlot *slots, int nslots, int64_t ti) {
+    int lo = 0, hi = nslots;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (slots[mid].tile0 <= ti) lo = mid;
+        else hi = mid;
+    }
+    return slots[lo];
+}
+
+__device__ __forceinline__ void bin_group_take(ScanParams &p, const GroupSlot &g, float *matrix) {
+    p.codes = g.codes;
+    p.n = g.n;
+    p.chunk_rows = g.granule;
+    p.filter = g.filter;
+    p.exists = g.exists;
+    p.row_begin = 0;
+    p.row_end = g.n;
+    p.tiles_per_chunk = 0;
+    p.tile_rows = kSmallRows;
+    p.probe = matrix + g.col0;
+}
+
+template <int METRIC, bool REG>
+__global__ __launch_bounds__(256) void k_scan_group_binary(ScanParams p, const GroupSlot *slots, int nslots,
+                                                           int64_t tiles) {
+    constexpr int QC = kBinQC, RW = kBinRW;
+    const int t = threadIdx.x;
+    const int W4 = p.code_words / 4;
+    const int nbits = p.nbits;
+    float *const matrix = p.probe;
+    // REG: the next tile's row (of the next tile's part) is in flight during
+    // this tile's popcounts, as in k_scan_binary
+    uint4 yn[RW];
+    auto load_row = [&](int64_t ti, uint4 (&dst)[RW]) {
+        const GroupSlot &g = bin_group_slot(slots, nslots, ti);
+        const int64_t r0 = (ti - g.tile0) * kSmallRows;
+        const int64_t r1 = r0 + kSmallRows < g.n ? r0 + kSmallRows : g.n;
+        bin_load_row(g.codes, p.code_words, W4, r0 + t, r1, dst);
+    };
+    if (REG && blockIdx.x < tiles) load_row(blockIdx.x, yn);
+    for (int64_t ti = blockIdx.x; ti < tiles; ti += gridDim.x) {
+        const GroupSlot &g = bin_group_slot(slots, nslots, ti);
+        bin_group_take(p, g, matrix);
+        int64_t r0, r1, chunk;
+        tile_range(p, ti - g.tile0, r0, r1, chunk);
+        const int64_t pos = r0 + t;
+        const bool inrange = pos < r1;
+        const bool valid_row = inrange && row_valid(p, pos);
+        const uint4 *yr = reinterpret_cast<const uint4 *>(p.codes + (inrange ? pos : 0) * p.code_words);
+        uint4 yc[RW];
+        if (REG) {
+#pragma unroll
+            for (int u = 0; u < RW; ++u) yc[u] = yn[u];
+            if (ti + gridDim.x < tiles) load_row(ti + gridDim.x, yn);
+        }
+        for (int j0 = 0; j0 < p.nq; j0 += QC) {
+            uint32_t a[QC], b[QC];
+            bin_row_pass<METRIC, REG>(p, j0, W4, yc, yr, inrange, a, b);
+#pragma unroll
+            for (int jj = 0; jj < QC; ++jj) {
+                const int j = j0 + jj;
+                if (j >= p.nq) break;  // wave-uniform
+                if (inrange)
+                    p.probe[(int64_t)j * p.probe_ld + pos] = bin_probe_value<METRIC>(a[jj], b[jj], valid_row, nbits);
+            }
+        }
+    }
+}
+
+template <int METRIC, int W4>
+__global__ __launch_bounds__(256) void k_scan_group_binary_co(ScanParams p, const GroupSlot *slots, int nslots,
+                                                              int64_t tiles) {
+    constexpr int QC = kBinQC;
+    const int t = threadIdx.x;
+    const int u = t & (W4 - 1);
+    const int nbits = p.nq > 0 ? p.nbits : 0;
+    float *const matrix = p.probe;
+    uint4 qv[QC];
+#pragma unroll
+    for (int jj = 0; jj < QC; ++jj)
+        qv[jj] = jj < p.nq ? reinterpret_cast<const uint4 *>(p.qcodes + (int64_t)jj * p.code_words)[u]
+                           : make_uint4(0u, 0u, 0u, 0u);
+    for (int64_t ti = blockIdx.x; ti < tiles; ti += gridDim.x) {
+        const GroupSlot &g = bin_group_slot(slots, nslots, ti);
+        bin_group_take(p, g, matrix);
+        const uint4 *base = reinterpret_cast<const uint4 *>(p.codes);
+        int64_t r0, r1, chunk;
+        tile_range(p, ti - g.tile0, r0, r1, chunk);
+        uint4 y[W4];
+#pragma unroll
+        for (int sidx = 0; sidx < W4; ++sidx) {
+            const int64_t row = r0 + (sidx * 256 + t) / W4;
+            y[sidx] = row < r1 ? base[r0 * W4 + sidx * 256 + t] : make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int sidx = 0; sidx < W4; ++sidx) {
+            const int64_t row = r0 + (sidx * 256 + t) / W4;
+            const bool inrange = row < r1;
+            const bool lead = u == 0;
+            const bool valid_row = lead && inrange && row_valid(p, row);
+#pragma unroll
+            for (int jj = 0; jj < QC; ++jj) {
+                if (jj >= p.nq) break;  // wave-uniform
+                uint32_t a, b;
+                bin_co_popc<METRIC, W4>(qv[jj], y[sidx], a, b);
+                if (lead && inrange)
+                    p.probe[(int64_t)jj * p.probe_ld + row] = bin_probe_value<METRIC>(a, b, valid_row, nbits);
+            }
+        }
+    }
+}
+
+template <int METRIC>
+static void scan_group_binary_t(const ScanParams &p, const GroupSlot *slots, int nslots, int64_t tiles,
+                                hipStream_t s) {
+    const int64_t grid = tiles < 4096 ? tiles : 4096;
+    if (grid < 1) return;
+    // the form scan_binary_t chooses for this nq and code width
+    if (p.nq <= 8 && !tune_env("MQVS_BIN_NOCO")) {
+        switch (p.code_words / 4) {
+            case 1:
+                hipLaunchKernelGGL((k_scan_group_binary_co<METRIC, 1>), dim3((unsigned)grid), dim3(256), 0, s, p, slots,
+                                   nslots, tiles);
+                return;
+            case 2:
+                hipLaunchKernelGGL((k_scan_group_binary_co<METRIC, 2>), dim3((unsigned)grid), dim3(256), 0, s, p, slots,
+                                   nslots, tiles);
+                return;
+            case 4:
+                hipLaunchKernelGGL((k_scan_group_binary_co<METRIC, 4>), dim3((unsigned)grid), dim3(256), 0, s, p, slots,
+                                   nslots, tiles);
+                return;
+            case 8:
+                hipLaunchKernelGGL((k_scan_group_binary_co<METRIC, 8>), dim3((unsigned)grid), dim3(256), 0, s, p, slots,
+                                   nslots, tiles);
+                return;
+            default: break;
+        }
+    }
+    if (p.code_words <= 32)
+        hipLaunchKernelGGL((k_scan_group_binary<METRIC, true>), dim3((unsigned)grid), dim3(256), 0, s, p, slots, nslots,
+                           tiles);
+    else
+        hipLaunchKernelGGL((k_scan_group_binary<METRIC, false>), dim3((unsigned)grid), dim3(256), 0, s, p, slots,
+                           nslots, tiles);
+}
+
+void launch_scan_group_binary(const ScanParams &base, const GroupSlot *slots, int nslots, int64_t tiles, int metric,
+                              hipStream_t s) {
+    if (metric == MQVS_METRIC_HAMMING)
+        scan_group_binary_t<MQVS_METRIC_HAMMING>(base, slots, nslots, tiles, s);
+    else
+        scan_group_binary_t<MQVS_METRIC_JACCARD>(base, slots, nslots, tiles, s);
 }
 
 // Hamming results of the faiss contract (mqvs_knn_binary_raw): float counts

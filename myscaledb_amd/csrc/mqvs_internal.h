@@ -254,7 +254,10 @@ __device__ inline bool row_valid(const ScanParams &p, int64_t r) {
 // [nq][ld] matrix; the grouped select reads each (slot, query) slice.  A
 // table of m slots ends with a sentinel whose tile0 is the launch's tile count.
 struct GroupSlot {
-    const float *rows;
+    union {
+        const float *rows;
+        const uint32_t *codes;  // binary parts: [n][code_words] (the segment's codes)
+    };
     const float *row_norms;   // the segment's |y|^2 per row (batch scan, L2)
     const int *chunk_ord;     // as ScanParams::chunk_ord
     const uint8_t *nonempty;
@@ -274,6 +277,11 @@ void launch_scan_group(const ScanParams &base, const GroupSlot *slots, int nslot
 // kMfmaRows rows; base also holds qnorms and num_qblocks
 void launch_scan_group_mfma(const ScanParams &base, const GroupSlot *slots, int nslots, int64_t tiles, int metric,
                             hipStream_t s);
+// binary parts (kernels_binary.hip): the PROBE values of k_scan_binary /
+// k_scan_binary_co, tiles of kSmallRows rows; base: nq, qcodes, code_words,
+// nbits, probe (the matrix), probe_ld set
+void launch_scan_group_binary(const ScanParams &base, const GroupSlot *slots, int nslots, int64_t tiles, int metric,
+                              hipStream_t s);
 // per (slot, query) the k best rows of the slice in mqvs_search's order ->
 // list_ids / list_dist [group parts][nq][k] at the slot's part
 void launch_select_group(const float *matrix, int64_t ld, const GroupSlot *slots, int nslots, int nq, int k,

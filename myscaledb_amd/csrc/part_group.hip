@@ -18,6 +18,11 @@
 // Parts the fused route does not take run mqvs_search's own path on the same
 // stream into their list of the same merge.  Nothing here depends on what a
 // kernel found: the call has one host wait, after the merge.
+//
+// A group of binary (FixedString) segments is searched by
+// mqvs_part_group_search_binary: the query codes uploaded once, steps 2 - 4
+// with k_scan_group_binary (the PROBE values of mqvs_search_binary's popcount
+// scans) and the L2 order, at any nq; the per-part route is search_binary.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -29,8 +34,10 @@
 struct mqvs_part_group {
     std::vector<mqvs_segment *> segs;
     int device = 0;
-    int d = 0;
+    int d = 0;  // binary: dim_bits
     bool cos = false;
+    bool binary = false;  // FixedString segments, all of one width
+    int code_bytes = 0, code_words = 0;
     int64_t rows = 0;
 };
 
@@ -46,6 +53,15 @@ static std::atomic<int64_t> g_group_rows{131072};
 // (0 = off, the default), max_nq above them (0 = no cap) -- one word, so a
 // search reads a pair some call set
 static std::atomic<int64_t> g_group_batch{0};
+// the fused route's row limit for binary parts (mqvs_set_part_group_binary_rows).
+// Up to 32768 rows search_binary itself probes the whole part densely (P = n,
+// search_binary.hip), so the fused route does the same device work per part
+// with fewer launches and no host wait per part.  Above that it was measured
+// with groups of 8 equal parts of 256-bit codes, k 100, Hamming and Jaccard
+// (profiles/part_group/binary_limit.jsonl): fused wins at nq 1, 16 and 128 up
+// to 131072 rows; at 262144 the per-part route (a short probe, then appends
+// under its threshold) wins at nq 1, at 524288 at every nq
+static std::atomic<int64_t> g_group_binary_rows{131072};
 static thread_local mqvs_part_group_stats t_group_stats{};
 
 static bool rows_fusable(const mqvs_segment *s, int64_t limit) { return !s->rows_host && s->n <= limit; }
@@ -60,9 +76,11 @@ static mqvs_part_group *group_create(const mqvs_segment_t *segs, int nparts) {
         if (!segs[p]) fail(MQVS_ERR_BAD_ARGUMENTS, "null segment in a part group");
     for (int p = 0; p < nparts; ++p) {
         const mqvs_segment *s = segs[p];
-        if (s->binary) fail(MQVS_ERR_LOGICAL, "binary (FixedString) segment in a part group: groups hold Float32 parts");
+        if (s->binary != segs[0]->binary)
+            fail(MQVS_ERR_LOGICAL, "binary (FixedString) and Float32 segments in one part group");
         if (s->d != segs[0]->d) fail(MQVS_ERR_LOGICAL, "segments of a part group differ in dimension");
-        if ((s->metric == MQVS_METRIC_COSINE) != (segs[0]->metric == MQVS_METRIC_COSINE))
+        // (a binary segment serves Hamming and Jaccard whatever its default metric)
+        if (!s->binary && (s->metric == MQVS_METRIC_COSINE) != (segs[0]->metric == MQVS_METRIC_COSINE))
             fail(MQVS_ERR_LOGICAL, "cosine and non-cosine segments in one part group");
         if (s->device != segs[0]->device) fail(MQVS_ERR_BAD_ARGUMENTS, "segments of a part group are on different devices");
     }
@@ -70,7 +88,10 @@ static mqvs_part_group *group_create(const mqvs_segment_t *segs, int nparts) {
     g->segs.assign(segs, segs + nparts);
     g->device = segs[0]->device;
     g->d = segs[0]->d;
-    g->cos = segs[0]->metric == MQVS_METRIC_COSINE;
+    g->binary = segs[0]->binary;
+    g->cos = !g->binary && segs[0]->metric == MQVS_METRIC_COSINE;
+    g->code_bytes = segs[0]->code_bytes;
+    g->code_words = segs[0]->code_words;
     for (int p = 0; p < nparts; ++p) g->rows += segs[p]->n;
     return g;
 }
@@ -82,10 +103,156 @@ static size_t bitmap_slot(size_t &total, int64_t n) {
     return off;
 }
 
+// slots [first_slot, first_slot + nslots) (+ the sentinel) of one grouped
+// scan + select: fused parts whose dense matrix fits the scratch budget
+struct Slice {
+    int first_slot, nslots;
+    int64_t tiles, cols;
+};
+
+// What the two group searches do the same way around their scans: the slot
+// tables of the fused parts cut into slices, the call's host inputs staged
+// with them in one copy, the per-part lists, and the merge with the call's
+// one host wait.
+struct GroupCall {
+    const mqvs_part_group *g;
+    Workspace &ws;
+    hipStream_t s;
+    bool dev;
+    int nq, k;
+    const uint8_t *const *filters;
+    const uint8_t *const *exists;
+    std::vector<Slice> slices;
+    std::vector<GroupSlot> slots;
+    std::vector<size_t> foff, eoff;
+    const GroupSlot *dslots = nullptr;
+    const uint8_t *dbits = nullptr;
+    const uint8_t *dextra = nullptr;  // stage()'s extra bytes on the device
+    int64_t *list_ids = nullptr;      // [nparts][nq][k]
+    float *list_dist = nullptr;
+    CallIO::Out out{};
+    int32_t *dpart = nullptr;
+
+    int nparts() const { return (int)g->segs.size(); }
+
+    // fill(p, e) sets the part's own fields of its slot and returns its tiles
+    template <typename Fill>
+    void build_slices(const std::vector<char> &fused, Fill &&fill) {
+        const int64_t max_cols = std::max<int64_t>(1, (int64_t)(scratch_budget() / (sizeof(float) * (size_t)nq)));
+        Slice cur{0, 0, 0, 0};
+        auto close = [&] {
+            if (cur.nslots == 0) return;
+            GroupSlot end{};
+            end.tile0 = cur.tiles;
+            end.col0 = cur.cols;
+            end.part = -1;
+            slots.push_back(end);
+            slices.push_back(cur);
+            cur = Slice{(int)slots.size(), 0, 0, 0};
+        };
+        for (int p = 0; p < nparts(); ++p) {
+            if (!fused[p]) continue;
+            const mqvs_segment *seg = g->segs[p];
+            if (cur.nslots > 0 && cur.cols + seg->n > max_cols) close();
+            GroupSlot e{};
+            e.n = seg->n;
+            e.granule = seg->granule;
+            e.row_offset = seg->row_offset;
+            e.tile0 = cur.tiles;
+            e.col0 = cur.cols;
+            e.part = p;
+            const int64_t tiles = fill(p, e);
+            slots.push_back(e);
+            cur.nslots += 1;
+            cur.tiles += tiles;
+            cur.cols += seg->n;
+        }
+        close();
+    }
+
+    // this call's bitmaps of part p on the device
+    const uint8_t *part_filter(int p) const {
+        return !(filters && filters[p]) ? nullptr : dev ? filters[p] : dbits + foff[p];
+    }
+    const uint8_t *part_exists(int p) const {
+        return !(exists && exists[p]) ? nullptr : dev ? exists[p] : dbits + eoff[p];
+    }
+
+    // the slot tables, the host bitmaps of every part and `extra` (host bytes
+    // of the call, or null) through one pinned buffer, one copy to the device
+    void stage(const void *extra, size_t extra_bytes) {
+        const int np = nparts();
+        foff.assign(np, (size_t)-1);
+        eoff.assign(np, (size_t)-1);
+        size_t bits_bytes = 0;
+        if (!dev)
+            for (int p = 0; p < np; ++p) {
+                if (filters && filters[p]) foff[p] = bitmap_slot(bits_bytes, g->segs[p]->n);
+                if (exists && exists[p]) eoff[p] = bitmap_slot(bits_bytes, g->segs[p]->n);
+            }
+        const size_t slot_bytes = (size_t)round_up((int64_t)(sizeof(GroupSlot) * slots.size()), 16);
+        const size_t total = slot_bytes + bits_bytes + (size_t)round_up((int64_t)extra_bytes, 16);
+        if (total == 0) return;
+        auto *pin = (unsigned char *)ws.pg_pin_in.get(total);
+        auto *dbuf = (unsigned char *)ws.pg_slots.get(total);
+        dslots = (const GroupSlot *)dbuf;
+        dbits = dbuf + slot_bytes;
+        dextra = dbuf + slot_bytes + bits_bytes;
+        for (int p = 0; p < np && !dev; ++p) {
+            const size_t bm = (size_t)((g->segs[p]->n + 7) / 8);
+            if (foff[p] != (size_t)-1) std::memcpy(pin + slot_bytes + foff[p], filters[p], bm);
+            if (eoff[p] != (size_t)-1) std::memcpy(pin + slot_bytes + eoff[p], exists[p], bm);
+        }
+        if (extra_bytes) std::memcpy(pin + slot_bytes + bits_bytes, extra, extra_bytes);
+        for (GroupSlot &e : slots) {
+            if (e.part < 0) continue;
+            e.filter = part_filter(e.part);
+            e.exists = part_exists(e.part);
+        }
+        if (!slots.empty()) std::memcpy(pin, slots.data(), sizeof(GroupSlot) * slots.size());
+        MQVS_HIP(hipMemcpyAsync(dbuf, pin, total, hipMemcpyHostToDevice, s));
+    }
+
+    // per-part lists [nparts][nq][k] and the outputs
+    void lists_and_outputs(int32_t *out_part, int64_t *out_ids, float *out_dist) {
+        const size_t nlist = (size_t)nparts() * nq * k, nout = (size_t)nq * k;
+        auto *lbuf = (unsigned char *)ws.pg_lists.get(nlist * 12 + 16);
+        list_ids = (int64_t *)lbuf;
+        list_dist = (float *)(lbuf + nlist * 8);
+        out = ws.io.out(nout, dev, out_ids, out_dist);
+        dpart = dev ? out_part : (int32_t *)ws.pg_part.get(sizeof(int32_t) * nout);
+    }
+    int64_t *part_ids(int p) const { return list_ids + (size_t)p * nq * k; }
+    float *part_dist(int p) const { return list_dist + (size_t)p * nq * k; }
+
+    // the merge (order: the metric whose key orders the lists), and the call's one wait
+    void merge_and_wait(int order, int32_t *out_part, mqvs_part_group_stats &st) {
+        const int np = nparts();
+        const size_t nout = (size_t)nq * k;
+        uint4 *scratch =
+            (int64_t)np * k > kSortCap ? (uint4 *)ws.pg_sort.get(sizeof(uint4) * 2 * (size_t)np * k * nq) : nullptr;
+        launch_merge_shards(np, nq, k, order, list_ids, list_dist, out.ids, out.dist, true, scratch, s, dpart);
+        MQVS_HIP(hipGetLastError());
+        st.launches += 1;
+        ws.io.finish_begin(out, s);
+        int32_t *hpart = nullptr;
+        if (!dev) {
+            hpart = (int32_t *)ws.pg_pin_out.get(sizeof(int32_t) * nout);
+            MQVS_HIP(hipMemcpyAsync(hpart, dpart, sizeof(int32_t) * nout, hipMemcpyDeviceToHost, s));
+        }
+        host_wait(s);
+        ws.io.finish_end(out);
+        if (hpart) std::memcpy(out_part, hpart, sizeof(int32_t) * nout);
+    }
+};
+
 static void group_search(mqvs_part_group *g, const float *queries, int nq, int k, int metric,
                          const uint8_t *const *filters, const uint8_t *const *exists, int32_t *out_part,
                          int64_t *out_ids, float *out_dist, uint32_t flags, hipStream_t user_stream) {
-    check_search_args(g, "part group", nullptr, nq, k, queries, out_ids, out_dist);
+    check_search_args(g, "part group",
+                      g && g->binary ? "binary (FixedString) part group: search it with mqvs_part_group_search_binary"
+                                     : nullptr,
+                      nq, k, queries, out_ids, out_dist);
     if (nq > 0 && k > 0 && !out_part) fail(MQVS_ERR_BAD_ARGUMENTS, "null query or output pointer");
     const bool cos = metric == MQVS_METRIC_COSINE;
     if (metric != MQVS_METRIC_L2 && metric != MQVS_METRIC_IP && !cos)
@@ -146,103 +313,32 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
     st.batch = batch && nfused > 0;
 
     // ---- inputs.  Host bitmaps: every part's into one pinned buffer behind
-    // the slot tables, one copy to the device
+    // the slot tables, one copy to the device (GroupCall::stage)
     const float *dq =
         (const float *)ws.io.in(queries, sizeof(float) * (size_t)nq * d, nullptr, nullptr, 0, dev, s).queries;
-    // slices of fused parts whose dense matrix fits the scratch budget
-    struct Slice {
-        int first_slot, nslots;
-        int64_t tiles, cols;
-    };
-    std::vector<Slice> slices;
-    std::vector<GroupSlot> slots;
-    const int64_t max_cols = std::max<int64_t>(1, (int64_t)(scratch_budget() / (sizeof(float) * (size_t)nq)));
-    std::vector<size_t> foff(nparts, (size_t)-1), eoff(nparts, (size_t)-1);
-    size_t bits_bytes = 0;
-    if (!dev)
-        for (int p = 0; p < nparts; ++p) {
-            if (filters && filters[p]) foff[p] = bitmap_slot(bits_bytes, g->segs[p]->n);
-            if (exists && exists[p]) eoff[p] = bitmap_slot(bits_bytes, g->segs[p]->n);
+    GroupCall c{g, ws, s, dev, nq, k, filters, exists};
+    c.build_slices(fused, [&](int p, GroupSlot &e) {
+        const mqvs_segment *seg = g->segs[p];
+        e.rows = seg->rows;
+        e.row_norms = seg->norms;
+        e.chunk_ord = seg->chunk_ord;
+        e.nonempty = seg->nonempty_bits;
+        // cosine and chunk-ordinal parts: tiles that never span two chunks
+        const bool aligned = cos || seg->chunk_ord != nullptr;
+        int64_t tiles = (seg->n + tile_rows - 1) / tile_rows;
+        if (aligned && seg->n > 0) {
+            // (a part shorter than its granule is one chunk: no tiles past its rows)
+            e.tiles_per_chunk = (std::min(seg->granule, seg->n) + tile_rows - 1) / tile_rows;
+            tiles = (seg->n + seg->granule - 1) / seg->granule * e.tiles_per_chunk;
         }
-    {
-        Slice cur{0, 0, 0, 0};
-        auto close = [&] {
-            if (cur.nslots == 0) return;
-            GroupSlot end{};
-            end.tile0 = cur.tiles;
-            end.col0 = cur.cols;
-            end.part = -1;
-            slots.push_back(end);
-            slices.push_back(cur);
-            cur = Slice{(int)slots.size(), 0, 0, 0};
-        };
-        for (int p = 0; p < nparts; ++p) {
-            if (!fused[p]) continue;
-            const mqvs_segment *seg = g->segs[p];
-            if (cur.nslots > 0 && cur.cols + seg->n > max_cols) close();
-            GroupSlot e{};
-            e.rows = seg->rows;
-            e.row_norms = seg->norms;
-            e.chunk_ord = seg->chunk_ord;
-            e.nonempty = seg->nonempty_bits;
-            e.n = seg->n;
-            e.granule = seg->granule;
-            e.row_offset = seg->row_offset;
-            e.tile0 = cur.tiles;
-            e.col0 = cur.cols;
-            e.part = p;
-            // cosine and chunk-ordinal parts: tiles that never span two chunks
-            const bool aligned = cos || seg->chunk_ord != nullptr;
-            int64_t tiles = (seg->n + tile_rows - 1) / tile_rows;
-            if (aligned && seg->n > 0) {
-                // (a part shorter than its granule is one chunk: no tiles past its rows)
-                e.tiles_per_chunk = (std::min(seg->granule, seg->n) + tile_rows - 1) / tile_rows;
-                tiles = (seg->n + seg->granule - 1) / seg->granule * e.tiles_per_chunk;
-            }
-            slots.push_back(e);
-            cur.nslots += 1;
-            cur.tiles += tiles;
-            cur.cols += seg->n;
-        }
-        close();
-    }
-    const size_t slot_bytes = (size_t)round_up((int64_t)(sizeof(GroupSlot) * slots.size()), 16);
-    const uint8_t *dbits = nullptr;
-    const GroupSlot *dslots = nullptr;
-    if (slot_bytes + bits_bytes > 0) {
-        auto *pin = (unsigned char *)ws.pg_pin_in.get(slot_bytes + bits_bytes);
-        auto *dbuf = (unsigned char *)ws.pg_slots.get(slot_bytes + bits_bytes);
-        dslots = (const GroupSlot *)dbuf;
-        dbits = dbuf + slot_bytes;
-        for (int p = 0; p < nparts && !dev; ++p) {
-            const size_t bm = (size_t)((g->segs[p]->n + 7) / 8);
-            if (foff[p] != (size_t)-1) std::memcpy(pin + slot_bytes + foff[p], filters[p], bm);
-            if (eoff[p] != (size_t)-1) std::memcpy(pin + slot_bytes + eoff[p], exists[p], bm);
-        }
-        // this call's bitmaps of part p on the device
-        for (GroupSlot &e : slots) {
-            if (e.part < 0) continue;
-            const int p = e.part;
-            e.filter = !(filters && filters[p]) ? nullptr : dev ? filters[p] : dbits + foff[p];
-            e.exists = !(exists && exists[p]) ? nullptr : dev ? exists[p] : dbits + eoff[p];
-        }
-        if (!slots.empty()) std::memcpy(pin, slots.data(), sizeof(GroupSlot) * slots.size());
-        MQVS_HIP(hipMemcpyAsync(dbuf, pin, slot_bytes + bits_bytes, hipMemcpyHostToDevice, s));
-    }
-    auto part_filter = [&](int p) -> const uint8_t * {
-        return !(filters && filters[p]) ? nullptr : dev ? filters[p] : dbits + foff[p];
-    };
-    auto part_exists = [&](int p) -> const uint8_t * {
-        return !(exists && exists[p]) ? nullptr : dev ? exists[p] : dbits + eoff[p];
-    };
-
-    // ---- per-part lists [nparts][nq][k] and the outputs
-    const size_t nlist = (size_t)nparts * nq * k, nout = (size_t)nq * k;
-    auto *lbuf = (unsigned char *)ws.pg_lists.get(nlist * 12 + 16);
-    auto *list_ids = (int64_t *)lbuf;
-    auto *list_dist = (float *)(lbuf + nlist * 8);
-    const CallIO::Out out = ws.io.out(nout, dev, out_ids, out_dist);
-    int32_t *dpart = dev ? out_part : (int32_t *)ws.pg_part.get(sizeof(int32_t) * nout);
+        return tiles;
+    });
+    c.stage(nullptr, 0);
+    c.lists_and_outputs(out_part, out_ids, out_dist);
+    const std::vector<Slice> &slices = c.slices;
+    const GroupSlot *dslots = c.dslots;
+    int64_t *list_ids = c.list_ids;
+    float *list_dist = c.list_dist;
 
     // ---- the fused route
     if (nfused > 0) {
@@ -292,26 +388,118 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
     // ---- the per-part route (each search ends in its own host wait)
     for (int p = 0; p < nparts; ++p) {
         if (fused[p]) continue;
-        search_segment(g->segs[p], dq, nq, k, metric, part_filter(p), part_exists(p), list_ids + (size_t)p * nq * k,
-                       list_dist + (size_t)p * nq * k, flags & ~(uint32_t)MQVS_F_ASYNC, s, -1);
+        search_segment(g->segs[p], dq, nq, k, metric, c.part_filter(p), c.part_exists(p), c.part_ids(p),
+                       c.part_dist(p), flags & ~(uint32_t)MQVS_F_ASYNC, s, -1);
     }
 
     // ---- the merge, and the call's one wait
-    uint4 *scratch = (int64_t)nparts * k > kSortCap
-                         ? (uint4 *)ws.pg_sort.get(sizeof(uint4) * 2 * (size_t)nparts * k * nq)
-                         : nullptr;
-    launch_merge_shards(nparts, nq, k, metric, list_ids, list_dist, out.ids, out.dist, true, scratch, s, dpart);
-    MQVS_HIP(hipGetLastError());
-    st.launches += 1;
-    ws.io.finish_begin(out, s);
-    int32_t *hpart = nullptr;
-    if (!dev) {
-        hpart = (int32_t *)ws.pg_pin_out.get(sizeof(int32_t) * nout);
-        MQVS_HIP(hipMemcpyAsync(hpart, dpart, sizeof(int32_t) * nout, hipMemcpyDeviceToHost, s));
+    c.merge_and_wait(metric, out_part, st);
+    if (timing)
+        st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    t_group_stats = st;
+}
+
+// mqvs_part_group_search_binary: the same call over binary parts.  Both binary
+// distances are ascending and finite, so select and merge run with the L2
+// order (as search_binary's own selects and mqvs_merge_shards do); there is no
+// formula switch at nq 20 and no chunk arithmetic, so one fused route serves
+// every nq and a filter never sends a part to the per-part route.
+static void group_search_binary(mqvs_part_group *g, const uint8_t *queries, int nq, int k, int metric,
+                                const uint8_t *const *filters, const uint8_t *const *exists, int32_t *out_part,
+                                int64_t *out_ids, float *out_dist, uint32_t flags, hipStream_t user_stream) {
+    check_search_args(g, "part group",
+                      g && !g->binary ? "Float32 part group: search it with mqvs_part_group_search" : nullptr, nq, k,
+                      queries, out_ids, out_dist);
+    if (nq > 0 && k > 0 && !out_part) fail(MQVS_ERR_BAD_ARGUMENTS, "null query or output pointer");
+    if (metric != MQVS_METRIC_HAMMING && metric != MQVS_METRIC_JACCARD)
+        fail(MQVS_ERR_NOT_IMPLEMENTED, "Metric not implemented in brute force search for Binary Vector");
+    const int nparts = (int)g->segs.size();
+    if ((int64_t)nparts * k > ((int64_t)1 << 20)) fail(MQVS_ERR_BAD_ARGUMENTS, "nparts * k above 2^20");
+    mqvs_part_group_stats st{};
+    st.parts = nparts;
+    st.nq = nq;
+    st.k = k;
+    t_group_stats = st;
+    if (nq == 0 || k == 0) return;
+    const bool timing = timing_on(flags);
+    const auto t0 = std::chrono::steady_clock::now();
+
+    DeviceGuard guard(g->device);
+    Workspace &ws = workspace(g->device);
+    WsCall ws_call(ws);
+    hipStream_t s = user_stream ? user_stream : ws.stream;
+    ws.last = s;
+    const bool dev = flags & MQVS_F_DEVICE_PTRS;
+    constexpr int kOrder = MQVS_METRIC_L2;  // ascending finite values: ord_asc key, (key, row) ties
+
+    // ---- the routes
+    const int64_t limit = g_group_binary_rows.load(std::memory_order_relaxed);
+    std::vector<char> fused(nparts, 0);
+    int nfused = 0;
+    for (int p = 0; p < nparts; ++p) {
+        fused[p] = k <= kSortCap && rows_fusable(g->segs[p], limit);
+        nfused += fused[p];
+        if (fused[p]) st.fused_rows += g->segs[p]->n;
     }
-    host_wait(s);
-    ws.io.finish_end(out);
-    if (hpart) std::memcpy(out_part, hpart, sizeof(int32_t) * nout);
+    st.fused_parts = nfused;
+    st.looped_parts = nparts - nfused;
+
+    // ---- inputs.  The host queries ride with the slot tables and bitmaps
+    GroupCall c{g, ws, s, dev, nq, k, filters, exists};
+    c.build_slices(fused, [&](int p, GroupSlot &e) {
+        e.codes = g->segs[p]->codes;
+        return (e.n + kSmallRows - 1) / kSmallRows;  // plain tiles from row 0 (no chunk arithmetic)
+    });
+    c.stage(dev ? nullptr : queries, dev ? 0 : (size_t)nq * g->code_bytes);
+    const uint8_t *dq = dev ? queries : c.dextra;  // [nq][code_bytes] on the device
+    c.lists_and_outputs(out_part, out_ids, out_dist);
+    const std::vector<Slice> &slices = c.slices;
+    const GroupSlot *dslots = c.dslots;
+    int64_t *list_ids = c.list_ids;
+    float *list_dist = c.list_dist;
+
+    // ---- the fused route
+    if (nfused > 0) {
+        int *fl = (int *)ws.pg_q.get(sizeof(int) * 8);  // [overflow 4][unused 4]
+        launch_fill2((uint32_t *)fl, 8, 0u, nullptr, 0, 0u, s);
+        MQVS_HIP(hipGetLastError());
+        st.launches += 1;
+        // the query codes, zero padded to the segments' row stride, once per call
+        uint32_t *qc = (uint32_t *)ws.pg_qvars.get((size_t)nq * g->code_words * 4);
+        upload_codes(qc, g->code_words, dq, g->code_bytes, nq, true, s);
+        int64_t ld = 0;
+        for (const Slice &sl : slices) ld = std::max(ld, sl.cols);
+        float *matrix = (float *)ws.pg_matrix.get(sizeof(float) * (size_t)nq * std::max<int64_t>(ld, 1));
+        ScanParams p{};
+        p.d = g->d;
+        p.nq = nq;
+        p.qcodes = qc;
+        p.code_words = g->code_words;
+        p.nbits = g->d;
+        p.probe = matrix;
+        for (const Slice &sl : slices) {
+            p.probe_ld = sl.cols;
+            if (sl.tiles > 0) {
+                launch_scan_group_binary(p, dslots + sl.first_slot, sl.nslots, sl.tiles, metric, s);
+                MQVS_HIP(hipGetLastError());
+                st.launches += 1;
+            }
+            launch_select_group(matrix, sl.cols, dslots + sl.first_slot, sl.nslots, nq, k, kOrder, list_ids, list_dist,
+                                fl, s);
+            MQVS_HIP(hipGetLastError());
+            st.launches += 1;
+        }
+    }
+
+    // ---- the per-part route (each search ends in its own host wait)
+    for (int p = 0; p < nparts; ++p) {
+        if (fused[p]) continue;
+        search_binary(g->segs[p], dq, nq, k, metric, c.part_filter(p), c.part_exists(p), c.part_ids(p), c.part_dist(p),
+                      (flags & ~(uint32_t)MQVS_F_ASYNC) | (uint32_t)MQVS_F_DEVICE_PTRS, s);
+    }
+
+    // ---- the merge, and the call's one wait
+    c.merge_and_wait(kOrder, out_part, st);
     if (timing)
         st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     t_group_stats = st;
@@ -343,7 +531,7 @@ int mqvs_part_group_info(mqvs_part_group_t group, int32_t *nparts, int64_t *rows
         if (rows) *rows = group->rows;
         if (d) *d = group->d;
         if (fusable_parts) {
-            const int64_t limit = g_group_rows.load(std::memory_order_relaxed);
+            const int64_t limit = (group->binary ? g_group_binary_rows : g_group_rows).load(std::memory_order_relaxed);
             int32_t f = 0;
             for (const mqvs_segment *s : group->segs) f += rows_fusable(s, limit);
             *fusable_parts = f;
@@ -361,6 +549,19 @@ int mqvs_part_group_search(mqvs_part_group_t group, const float *queries, int32_
                       row_exists != nullptr, flags};
         group_search(group, queries, nq, k, metric, filters, row_exists, out_part, out_ids, out_dist, flags,
                      (hipStream_t)stream);
+    });
+}
+
+int mqvs_part_group_search_binary(mqvs_part_group_t group, const uint8_t *queries, int32_t nq, int32_t k,
+                                  int32_t metric, const uint8_t *const *filters, const uint8_t *const *row_exists,
+                                  int32_t *out_part, int64_t *out_ids, float *out_dist, uint32_t flags,
+                                  mqvs_stream_t stream) {
+    return guarded([&] {
+        fault_point();
+        WaitScope wsc{10, (uint64_t)(uintptr_t)group, (uint64_t)nq, (uint64_t)k, (uint64_t)metric, filters != nullptr,
+                      row_exists != nullptr, flags};
+        group_search_binary(group, queries, nq, k, metric, filters, row_exists, out_part, out_ids, out_dist, flags,
+                            (hipStream_t)stream);
     });
 }
 
@@ -387,6 +588,12 @@ int mqvs_part_group_batch(int64_t *rows, int32_t *max_nq) {
 int64_t mqvs_set_part_group_rows(int64_t rows) {
     const int64_t prev = g_group_rows.load(std::memory_order_relaxed);
     if (rows > 0) g_group_rows.store(std::min<int64_t>(rows, kGroupRowsMax), std::memory_order_relaxed);
+    return prev;
+}
+
+int64_t mqvs_set_part_group_binary_rows(int64_t rows) {
+    const int64_t prev = g_group_binary_rows.load(std::memory_order_relaxed);
+    if (rows > 0) g_group_binary_rows.store(std::min<int64_t>(rows, kGroupRowsMax), std::memory_order_relaxed);
     return prev;
 }
 

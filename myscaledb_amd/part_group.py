@@ -6,6 +6,8 @@
 ``merge_shards(..., part_merge=True)`` returns, bit for bit, plus the part
 each result came from -- the labelled rows the reference's
 getTotalTopSearchResultImpl hands on (MergeTreeBaseSearchManager.cpp:207-297).
+``BinaryPartGroup`` is the same over ``BinaryVectorScanSegment`` parts
+(FixedString codes, Hamming / Jaccard; mqvs_part_group_search_binary).
 """
 from __future__ import annotations
 
@@ -22,6 +24,13 @@ def set_part_group_rows(rows: int) -> int:
     """Row limit of the fused route (mqvs_set_part_group_rows): parts of more
     rows take the per-part route.  Returns the previous value; 0 only reads it."""
     return int(lib.mqvs_set_part_group_rows(int(rows)))
+
+
+def set_part_group_binary_rows(rows: int) -> int:
+    """Row limit of a binary group's fused route
+    (mqvs_set_part_group_binary_rows).  Returns the previous value; 0 only
+    reads it."""
+    return int(lib.mqvs_set_part_group_binary_rows(int(rows)))
 
 
 def set_part_group_batch(rows: int, max_nq: int = 0) -> None:
@@ -49,6 +58,16 @@ def last_stats():
 class PartGroup:
     """An ordered list of VectorScanSegments (the part order of the merge).
     The group borrows the segments: keep them alive while it is used."""
+
+    _search_fn = "mqvs_part_group_search"
+    _torch_dtype = "float32"
+    _host = staticmethod(_host_f32)
+
+    def _width(self):
+        return self.d
+
+    def _width_error(self, got):
+        return f"query dimension {got} != column dimension {self.d}"
 
     def __init__(self, segments):
         self.segments = list(segments)
@@ -85,32 +104,34 @@ class PartGroup:
         CUDA uint8 tensors and the results come back as tensors."""
         m = self.metric if metric is None else metric_id(metric)
         extra = F_TIMING if timing else 0
+        fn = getattr(lib, self._search_fn)
         if _is_torch(queries):
             import torch
-            assert queries.is_cuda and queries.is_contiguous() and queries.dtype == torch.float32
+            assert queries.is_cuda and queries.is_contiguous() and queries.dtype == getattr(torch, self._torch_dtype)
+            if queries.shape[1] != self._width():
+                raise _lib.MqvsError(_lib.ERR_LOGICAL, self._width_error(queries.shape[1]))
             nq = queries.shape[0]
             part = torch.empty((nq, k), dtype=torch.int32, device=queries.device)
             ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
             dist = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
             fa, keep_f = self._bitmaps(filters, True)
             ea, keep_e = self._bitmaps(row_exists, True)
-            check(lib.mqvs_part_group_search(self._h, _ptr(queries), nq, k, m, fa, ea, _ptr(part), _ptr(ids),
-                                             _ptr(dist), F_DEVICE_PTRS | extra, None))
+            check(fn(self._h, _ptr(queries), nq, k, m, fa, ea, _ptr(part), _ptr(ids), _ptr(dist),
+                     F_DEVICE_PTRS | extra, None))
             del keep_f, keep_e
             return part, ids, dist
-        q = _host_f32(queries)
+        q = self._host(queries)
         if q.ndim == 1:
             q = q[None, :]
         nq = q.shape[0]
-        if q.shape[1] != self.d:
-            raise _lib.MqvsError(_lib.ERR_LOGICAL, f"query dimension {q.shape[1]} != column dimension {self.d}")
+        if q.shape[1] != self._width():
+            raise _lib.MqvsError(_lib.ERR_LOGICAL, self._width_error(q.shape[1]))
         part = np.empty((nq, k), np.int32)
         ids = np.empty((nq, k), np.int64)
         dist = np.empty((nq, k), np.float32)
         fa, keep_f = self._bitmaps(filters, False)
         ea, keep_e = self._bitmaps(row_exists, False)
-        check(lib.mqvs_part_group_search(self._h, _ptr(q), nq, k, m, fa, ea, _ptr(part), _ptr(ids), _ptr(dist),
-                                         extra, None))
+        check(fn(self._h, _ptr(q), nq, k, m, fa, ea, _ptr(part), _ptr(ids), _ptr(dist), extra, None))
         del keep_f, keep_e
         return part, ids, dist
 
@@ -126,3 +147,24 @@ class PartGroup:
             self.free()
         except Exception:
             pass
+
+
+class BinaryPartGroup(PartGroup):
+    """An ordered list of BinaryVectorScanSegments of one FixedString(N) width
+    (mqvs_part_group_search_binary).  ``search`` takes uint8 codes [nq, N]
+    (numpy, or a torch CUDA uint8 tensor) and Hamming or Jaccard (default: the
+    first segment's metric)."""
+
+    _search_fn = "mqvs_part_group_search_binary"
+    _torch_dtype = "uint8"
+    _host = staticmethod(_host_u8)
+
+    def __init__(self, segments):
+        super().__init__(segments)
+        self.nbytes = self.segments[0].nbytes
+
+    def _width(self):
+        return self.nbytes
+
+    def _width_error(self, got):
+        return f"query length {got} bytes != column FixedString({self.nbytes})"

@@ -28,6 +28,13 @@ and whether c_on wins against b and against c_off: its median is below the
 other's by more than both spreads.  With --batch, --limit-sweep times c_on
 against c_off for groups of 8 equal parts per part size and nq.
 
+--binary is the same method (variants a, b, c_host, c_dev and --limit-sweep)
+for binary parts: generated FixedString codes of --code-bits bits (default
+256), mqvs_search_binary per part against mqvs_part_group_search_binary,
+Hamming and Jaccard, default nq 1, 16, 128; the limit sweep sets
+mqvs_set_part_group_binary_rows.  Each record carries whether c_dev wins
+against b: its median is below b's by more than both variants' spreads.
+
 One JSON line per measurement on stdout (and --out)."""
 import argparse
 import ctypes
@@ -60,11 +67,7 @@ class Table:
         from myscaledb_amd import _lib
         self.mq, self.lib, self._lib = mq, _lib.lib, _lib
         self.nparts, self.nq, self.k, self.m = nparts, nq, k, _lib.METRICS[metric]
-        self.segs = [mq.VectorScanSegment.generate(seed + p, 1, rows, d, metric=metric, granule=8192)
-                     for p in range(nparts)]
-        self.group = mq.PartGroup(self.segs)
-        rng = np.random.default_rng(seed)
-        self.q = rng.standard_normal((nq, d)).astype(np.float32)
+        self.make(mq, nparts, rows, d, metric, nq, seed)
         self.tq = torch.from_numpy(self.q).cuda()
         sh = (nparts, nq, k)
         self.h_ids, self.h_dist = np.empty(sh, np.int64), np.empty(sh, np.float32)
@@ -79,12 +82,20 @@ class Table:
         self.hp = [(ptr(self.h_ids[p]), ptr(self.h_dist[p])) for p in range(nparts)]
         self.tp = [(ptr(self.t_ids[p]), ptr(self.t_dist[p])) for p in range(nparts)]
 
+    def make(self, mq, nparts, rows, d, metric, nq, seed):
+        """the segments, their group, the host queries and the two search calls"""
+        self.segs = [mq.VectorScanSegment.generate(seed + p, 1, rows, d, metric=metric, granule=8192)
+                     for p in range(nparts)]
+        self.group = mq.PartGroup(self.segs)
+        self.q = np.random.default_rng(seed).standard_normal((nq, d)).astype(np.float32)
+        self.search, self.group_search = self.lib.mqvs_search, self.lib.mqvs_part_group_search
+
     def run(self, v):
         L, _lib, nq, k, m = self.lib, self._lib, self.nq, self.k, self.m
         if v == "a":
             qp = ptr(self.q)
             for s, (ip, dp) in zip(self.segs, self.hp):
-                _lib.check(L.mqvs_search(s._h, qp, nq, k, m, None, None, ip, dp, 0, None))
+                _lib.check(self.search(s._h, qp, nq, k, m, None, None, ip, dp, 0, None))
             o = self.out["a"]
             _lib.check(L.mqvs_merge_shards(self.nparts, nq, k, m, ptr(self.h_ids), ptr(self.h_dist), ptr(o[1]),
                                            ptr(o[2]), _lib.F_PART_MERGE, None))
@@ -92,19 +103,19 @@ class Table:
             qp = ptr(self.tq)
             fl = _lib.F_DEVICE_PTRS | _lib.F_ASYNC
             for s, (ip, dp) in zip(self.segs, self.tp):
-                _lib.check(L.mqvs_search(s._h, qp, nq, k, m, None, None, ip, dp, fl, None))
+                _lib.check(self.search(s._h, qp, nq, k, m, None, None, ip, dp, fl, None))
             o = self.tout["b"]
             _lib.check(L.mqvs_merge_shards(self.nparts, nq, k, m, ptr(self.t_ids), ptr(self.t_dist), ptr(o[1]),
                                            ptr(o[2]), fl | _lib.F_PART_MERGE, None))
             _lib.check(L.mqvs_async_check(None))
         elif v == "c_host":
             o = self.out["c_host"]
-            _lib.check(L.mqvs_part_group_search(self.group._h, ptr(self.q), nq, k, m, None, None, ptr(o[0]),
-                                                ptr(o[1]), ptr(o[2]), 0, None))
+            _lib.check(self.group_search(self.group._h, ptr(self.q), nq, k, m, None, None, ptr(o[0]), ptr(o[1]),
+                                         ptr(o[2]), 0, None))
         else:
             o = self.tout["c_dev"]
-            _lib.check(L.mqvs_part_group_search(self.group._h, ptr(self.tq), nq, k, m, None, None, ptr(o[0]),
-                                                ptr(o[1]), ptr(o[2]), _lib.F_DEVICE_PTRS, None))
+            _lib.check(self.group_search(self.group._h, ptr(self.tq), nq, k, m, None, None, ptr(o[0]), ptr(o[1]),
+                                         ptr(o[2]), _lib.F_DEVICE_PTRS, None))
 
     def results(self, v):
         if v in self.out:
@@ -115,6 +126,18 @@ class Table:
         self.group.free()
         for s in self.segs:
             s.free()
+
+
+class BinaryTable(Table):
+    """the same over generated binary parts: d is the code width in bits"""
+
+    def make(self, mq, nparts, rows, d, metric, nq, seed):
+        rng = np.random.default_rng(seed)
+        self.segs = [mq.BinaryVectorScanSegment.from_codes(rng.integers(0, 256, (rows, d // 8), dtype=np.uint8),
+                                                           metric=metric, granule=8192) for _ in range(nparts)]
+        self.group = mq.BinaryPartGroup(self.segs)
+        self.q = rng.integers(0, 256, (nq, d // 8), dtype=np.uint8)
+        self.search, self.group_search = self.lib.mqvs_search_binary, self.lib.mqvs_part_group_search_binary
 
 
 def time_variants(run, variants, warmup, rounds):
@@ -216,12 +239,24 @@ def main():
     ap.add_argument("--variants", default="a,b,c_host,c_dev")
     ap.add_argument("--limit-sweep", default="", help="part sizes ROWS,... of the row-limit sweep (8 parts each)")
     ap.add_argument("--batch", action="store_true", help="the batch route: b, c_off, c_on at nq >= 20 (see above)")
+    ap.add_argument("--binary", action="store_true", help="binary parts (see above)")
+    ap.add_argument("--code-bits", type=int, default=256, help="--binary: code width in bits (a multiple of 8)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
 
     import myscaledb_amd as mq
-    from myscaledb_amd.part_group import last_stats, set_part_group_rows
+    from myscaledb_amd.part_group import last_stats, set_part_group_binary_rows, set_part_group_rows
     mq.init(0)
+    make_table, set_rows, sweep_metrics = Table, set_part_group_rows, ["L2"]
+    if args.binary:
+        if args.batch:
+            raise SystemExit("--binary has no batch route: one fused route serves every nq")
+        make_table, set_rows, args.dim = BinaryTable, set_part_group_binary_rows, args.code_bits
+        if args.metrics == "L2,Cosine":
+            args.metrics = "Hamming,Jaccard"
+        if args.nqs == "1,16":
+            args.nqs = "1,16,128"
+        sweep_metrics = args.metrics.split(",")
     sink = open(args.out, "w") if args.out else None
 
     def emit(rec):
@@ -242,7 +277,7 @@ def main():
         nparts, rows = (int(x) for x in case.split("x"))
         for metric in args.metrics.split(","):
             for nq in (int(x) for x in args.nqs.split(",")):
-                tb = Table(mq, nparts, rows, args.dim, metric, nq, args.k)
+                tb = make_table(mq, nparts, rows, args.dim, metric, nq, args.k)
                 try:
                     res = time_variants(tb.run, variants, args.warmup, args.rounds)
                     same = None
@@ -259,25 +294,31 @@ def main():
                     if any(v.startswith("c") for v in variants):
                         tb.run([v for v in variants if v.startswith("c")][0])
                         st = last_stats()
-                    emit(dict(kind="case", parts=nparts, rows=rows, d=args.dim, nq=nq, k=args.k, metric=metric,
-                              times=res, equals_a=same, group_stats=st))
+                    rec = dict(kind="case", parts=nparts, rows=rows, d=args.dim, nq=nq, k=args.k, metric=metric,
+                               times=res, equals_a=same, group_stats=st)
+                    if args.binary and "b" in res and "c_dev" in res:
+                        rec["c_dev_wins"] = dict(b=wins(res, "c_dev", "b"))
+                    emit(rec)
                     if same and not all(same.values()):
                         raise SystemExit(f"outputs differ from variant a: {same}")
                 finally:
                     tb.free()
 
-    for rows in [int(x) for x in args.limit_sweep.split(",") if x]:
+    for rows, metric in [(int(x), mt) for x in args.limit_sweep.split(",") if x for mt in sweep_metrics]:
         for nq in (int(x) for x in args.nqs.split(",")):
-            tb = Table(mq, 8, rows, args.dim, "L2", nq, args.k)
-            prev = set_part_group_rows(0)
+            tb = make_table(mq, 8, rows, args.dim, metric, nq, args.k)
+            prev = set_rows(0)
             try:
                 def run(v):
-                    set_part_group_rows(rows if v == "fused" else 1)
+                    set_rows(rows if v == "fused" else 1)
                     tb.run("c_dev")
                 res = time_variants(run, ["fused", "per_part"], args.warmup, args.rounds)
-                emit(dict(kind="limit", parts=8, rows=rows, d=args.dim, nq=nq, k=args.k, metric="L2", times=res))
+                rec = dict(kind="limit", parts=8, rows=rows, d=args.dim, nq=nq, k=args.k, metric=metric, times=res)
+                if args.binary:
+                    rec["fused_wins"] = wins(res, "fused", "per_part")
+                emit(rec)
             finally:
-                set_part_group_rows(prev)
+                set_rows(prev)
                 tb.free()
     if sink:
         sink.close()
