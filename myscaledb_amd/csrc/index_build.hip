@@ -81,7 +81,7 @@ void check_index_width(mqvs_segment *seg) {
 // From the centroids (ix->cent for a float index, ix->bcent for a binary one)
 // and the canonical assignment -- assign[n] on the device: each row's list, -1
 // for a row in no list -- to the finished index: the rows grouped by list on
-// the device (kernels_ivf.hip: k_grp_*), then everything derived from that:
+// the device (kernels_ivf_build.hip: k_grp_*), then everything derived from that:
 // the list plane (bf16, or fp8 codes + scale exponents) and |y|^2 in list
 // order, the plane's norm maxima and the coarse quantizer's centroid lists
 // (float), or the codes in list order (binary).  ix: seg, binary, metric,

@@ -11,7 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "mqvs_internal.h"
+#include "index_kernels.h"
 
 struct mqvs_index {
     mqvs_segment *seg = nullptr;   // borrowed: the caller keeps the segment alive

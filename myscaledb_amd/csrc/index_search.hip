@@ -7,7 +7,7 @@
 //   coarse   FLAT search of the queries against the centroid segment, k =
 //            nprobe (L2 for L2 parts, raw inner product for IP and cosine)
 //   plan     (query, list) pairs grouped by list into 16-query work items
-//   scan     bf16 MFMA over each probed list (kernels_ivf.hip); an index built
+//   scan     bf16 MFMA over each probed list (kernels_ivf_scan.hip); an index built
 //            with plane=fp8 keeps e4m3fn codes there, widened in registers
 //   select   num_reorder best approximate values per query
 //   re-rank  exact fp32 distances of those rows (k_rerank_ids: the formula

@@ -26,7 +26,7 @@
 // the segment and in the list-ordered copy alike.
 #include <cstdlib>
 
-#include "mqvs_internal.h"
+#include "index_kernels.h"
 #include "select_common.h"
 
 namespace mqvs {

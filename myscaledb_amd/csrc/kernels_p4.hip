@@ -59,7 +59,7 @@
 // k_probe_select_wide turns it into an append threshold with the same
 // guarantee as the dense probe matrix it replaces (at nq 1000: 2.8 MB written
 // instead of 360 MB); the main scan then covers the probe rows too.
-// GRP = 8 (PROBE only; the index's coarse step, kernels_ivf.hip
+// GRP = 8 (PROBE only; the index's coarse step, kernels_ivf_pick.hip
 // k_coarse_pick): one value per (query, 8-row half block) instead,
 // p4_gmax[q][2 (16 t + 8 wr + rb) + h].
 //

@@ -37,7 +37,7 @@
 //                                      pair-mode scan would run
 //   MQVS_IVF_COARSE      2 (else by    coarse step: 2 pick, 1 FLAT search of  index.hip search_index_impl
 //                        nlist)        the centroids, 0 list pass
-//   MQVS_PICK_TRACE      0             1: k_coarse_pick prints phase          kernels_ivf.hip launch_coarse_pick
+//   MQVS_PICK_TRACE      0             1: k_coarse_pick prints phase          kernels_ivf_pick.hip launch_coarse_pick
 //                                      timestamps of three workgroups
 //   MQVS_RR_1W_NQ        16            largest nq of k_exact_records_1w       kernels_rerank.hip launch_exact_rerank
 //   MQVS_BIN_GRID        4096          workgroup cap of the binary scan       kernels_binary.hip

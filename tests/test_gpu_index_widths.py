@@ -1,7 +1,7 @@
 """The index path (mqvs_index_*) at wide rows: d in {320, 1024, 1216, 1536, 2048,
 3072} and the widest accepted, 5056.
 
-The list scan (k_ivf_scan, kernels_ivf.hip) keeps a tile of 16 QB bf16
+The list scan (k_ivf_scan, kernels_ivf_scan.hip) keeps a tile of 16 QB bf16
 queries in LDS: 16 QB (2 dpad + 16) bytes of dynamic LDS + 256 QB static.
 list_pass (index_search.hip) wants 64-query items when lists average >= 40 probing
 queries (E = nq nprobe >= 40 nlist), 32 from 24 and on every dense pass, 16
@@ -98,6 +98,33 @@ def test_index_wide_query_group_forms_agree(mq, d, metric):
     assert (out[40][0] >= 0).all()
     for nq in (100, 200):
         same_bits((out[nq][0][:40], out[nq][1][:40]), out[40], f"qg d={d} {metric} batch {nq}")
+
+
+@pytest.mark.parametrize("metric", ["L2", "IP", "Cosine"])
+@pytest.mark.parametrize("plane", ["bf16", "fp8"])
+def test_index_64_query_tile_opt_in(mq, plane, metric):
+    """The 64-query tile at d 768 needs 64 (2 * 768 + 16) = 99328 B of dynamic
+    LDS, above the 65536 B a kernel gets without opting in: launch_ivf_scan
+    opts the plane's three scans in before the launch, and a scan it missed
+    fails its launch.  2048 rows, 4 lists, nprobe 4, first stage only: queries
+    0..2 alone (E = 12: 16-query items) and inside the batch of 40 (E = 160 =
+    40 nlist: 64-query items) return the same ids and value bits -- a query's
+    first-stage value does not depend on its tile (as
+    test_index_wide_pair_mode relies on)."""
+    n, d, nlist, k = 2048, 768, 4, 20
+    q = O.generate(SEED, 2, n, 40, d)
+    seg = mq.VectorScanSegment.generate(SEED, 2, n, d, metric=metric, granule=1024)
+    idx = mq.VectorIndex.build(seg, "MSTG", {"nlist": nlist, "plane": plane})
+    try:
+        out = {}
+        for nq in (3, 40):
+            out[nq] = idx.search(q[:nq], k, {"nprobe": 4}, first_stage_only=True)
+            st = mq.vector_index.last_index_stats()
+            assert st["pairs"] == 4 * nq, st
+    finally:
+        idx.free()
+        seg.free()
+    same_bits((out[40][0][:3], out[40][1][:3]), out[3], f"64-query tile {plane} {metric}")
 
 
 def test_index_wide_pair_mode(mq):

@@ -1,7 +1,7 @@
 // fp8_mfma_probe.hip -- how v_mfma_f32_16x16x32_fp8_fp8 (OCP e4m3fn operands)
 // sums the 32 products of one instruction on gfx950, and what
 // v_cvt_pk_fp8_f32 / v_cvt_scalef32_pk_bf16_fp8 do at the edges of the format.
-// Why the fp8 list scan (k_ivf_scan_fp8, kernels_ivf.hip) widens its codes to
+// Why the fp8 list scan (k_ivf_scan_fp8, kernels_ivf_scan.hip) widens its codes to
 // bf16 and uses the bf16 MFMA: see the output kept in
 // profiles/index_fp8/fp8_mfma_probe.log.
 //
