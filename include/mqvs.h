@@ -392,6 +392,93 @@ int64_t mqvs_set_part_group_binary_rows(int64_t rows);
 int mqvs_set_part_group_batch(int64_t rows, int32_t max_nq);
 int mqvs_part_group_batch(int64_t *rows, int32_t *max_nq);
 
+/* ---- index groups: many binary indexed parts in one fused call
+ * The parts of a table that carry a BINARYMSTG index (mqvs_index_build, below)
+ * are searched one by one by the reference and merged
+ * (MergeTreeSelectWithHybridSearchProcessor.cpp:1212-1241,
+ * MergeTreeBaseSearchManager.cpp:207-297).  An index group is an ordered list
+ * of binary indexes -- the list order is the part order of the merge -- and
+ * mqvs_index_group_search_binary returns, for every input, exactly what
+ *     mqvs_index_search_binary(indexes[p], queries, nq, k, params_p,
+ *         filters[p], row_exists[p]) for every p, then
+ *     mqvs_merge_shards(nparts, ..., MQVS_F_PART_MERGE) over the lists in
+ *         group order
+ * returns: ids (row_offset + row, then the part's row-ids map), distance bits
+ * and order (ascending by distance, then part, then position in the part's
+ * list) match bit for bit; padding slots hold id -1 and FLT_MAX, and out_part
+ * the group position of each result, -1 in padding slots.
+ * params_p is params with one change: an explicit nprobe (1..4096) is replaced
+ * by min(nprobe, nlist of part p) -- the parts of one table differ in their
+ * list counts, and mqvs_index_search_binary refuses nprobe > nlist; a part
+ * whose nprobe reaches its nlist is searched exhaustively.  Without nprobe each
+ * part resolves its own from alpha, as its own call does.  metric: one search
+ * metric for all parts (default: the first index's); num_reorder is accepted
+ * and ignored; an unknown key -> MQVS_ERR_BAD_ARGUMENTS.
+ *
+ * The group borrows the indexes and their segments (keep them alive while it
+ * is used); it copies nothing, makes no device pass and holds no device memory
+ * (hbm_bytes = 0).  Every search reads the live indexes, so a row-ids map
+ * registered after mqvs_index_group_create is honoured.
+ * Errors of mqvs_index_group_create: nparts < 1, a null handle, or indexes on
+ * different devices -> MQVS_ERR_BAD_ARGUMENTS; indexes of different dim_bits ->
+ * MQVS_ERR_LOGICAL; a Float32 index in the list -> MQVS_ERR_NOT_IMPLEMENTED
+ * (float index groups are not built).
+ * mqvs_index_group_info: rows = the sum of the segments' rows; lists = the sum
+ * of the indexes' nlist.  Any output pointer may be NULL.
+ *
+ * queries: nq x dim_bits / 8 bytes.  filters / row_exists: host arrays of
+ * nparts pointers to packed bitmaps (bit r % 8 of byte r / 8 = row r of the
+ * part); either array, or any entry, may be NULL.  With MQVS_F_DEVICE_PTRS the
+ * queries, the outputs and the bitmaps the entries point to are device
+ * pointers (the arrays themselves stay on the host).  MQVS_F_ASYNC is ignored
+ * (one host wait, after the merge); MQVS_F_FIRST_STAGE is accepted and returns
+ * the same result.  k: 1..16384; nparts * k > 2^20 -> MQVS_ERR_BAD_ARGUMENTS.
+ * mqvs_inject_fault is honoured (the outputs untouched), the call has a wait
+ * history of its own, and its scratch lives in the thread's workspace, behind
+ * the workspace budget gate.
+ * Two routes, the same bits on both:
+ *   fused     k <= 4096 and the part's scratch -- nq x (cap_p x 8 +
+ *             (nprobe_p < nlist_p ? 4 nlist_p : 0)) bytes, cap_p =
+ *             min(nprobe_p x max_list_p, npos_p) records per query -- fits
+ *             mqvs_set_scratch_budget, at any nq.  The query codes are
+ *             uploaded once; the fused parts are cut into slices whose summed
+ *             scratch fits the budget; per slice one grouped centroid-distance
+ *             kernel, one grouped pick, one grouped list scan and one grouped
+ *             select; then one grouped id map (only if a fused part has a
+ *             row-ids map), one stats kernel, the merge and one host wait.
+ *             The launch count does not depend on nparts.  A record region
+ *             holds every position of its probed lists: nothing overflows and
+ *             nothing is re-run.
+ *   per part  everything else (k > 4096, a part whose own scratch passes the
+ *             budget): mqvs_index_search_binary's own path on the same stream
+ *             with the resolved nprobe (it sub-batches the queries); the list
+ *             joins the same merge. */
+typedef struct mqvs_index_group *mqvs_index_group_t;
+int mqvs_index_group_create(const mqvs_index_t *indexes, int32_t nparts, mqvs_index_group_t *out);
+int mqvs_index_group_free(mqvs_index_group_t group);
+int mqvs_index_group_info(mqvs_index_group_t group, int32_t *nparts, int64_t *rows, int32_t *dim_bits,
+                          int64_t *lists, size_t *hbm_bytes);
+int mqvs_index_group_search_binary(mqvs_index_group_t group, const uint8_t *queries, int32_t nq, int32_t k,
+                                   const char *params, const uint8_t *const *filters,
+                                   const uint8_t *const *row_exists, int32_t *out_part, int64_t *out_ids,
+                                   float *out_dist, uint32_t flags, mqvs_stream_t stream);
+/* Stats of the calling thread's last mqvs_index_group_search_binary. */
+typedef struct {
+    double total_ms;      /* host time of the call (only with mqvs_set_timing(1) or MQVS_F_TIMING) */
+    int64_t values;       /* sums over the fused parts of the per-part index stats */
+    int64_t items;        /*   (mqvs_index_search_stats): records kept, non-empty work items, */
+    int64_t plane_bytes;  /*   list-plane bytes of the probed lists, (query, list) pairs */
+    int64_t pairs;
+    int32_t parts;
+    int32_t fused_parts;
+    int32_t looped_parts; /* parts searched by the per-part route */
+    int32_t launches;     /* kernel launches the call queued for the fused route and the merge
+                             (the per-part searches' own launches are not counted) */
+    int32_t nq;
+    int32_t k;
+} mqvs_index_group_stats;
+int mqvs_index_group_last_stats(mqvs_index_group_stats *out);
+
 /* ---- column ingest: a part's Array(Float32) column from its compressed files
  * Replaces the per-granule host read + copy of vectorScanWithoutIndex
  * (MergeTreeVSManager.cpp:1348-1393): data_bin = the bytes of the nested

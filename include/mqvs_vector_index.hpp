@@ -1069,4 +1069,93 @@ private:
     int32_t code_bytes = 0;
 };
 
+/// The parts of a FixedString(N) column that carry a BINARYMSTG index, searched
+/// in one fused call (mqvs_index_group_search_binary): the per-part
+/// BinaryGpuIndex::search calls and mergePartResults in one launch chain and
+/// one host wait.  The group borrows the indexes and their parts, which must
+/// outlive it, and reads them at every search (a row-ids map set later is
+/// honoured); the list order is the part order of the merge.
+class BinaryIndexGroup
+{
+public:
+    explicit BinaryIndexGroup(const std::vector<const BinaryGpuIndex *> & indexes)
+    {
+        std::vector<mqvs_index_t> hs;
+        for (const BinaryGpuIndex * ix : indexes)
+            hs.push_back(ix ? ix->handle() : nullptr);
+        mqvs_index_group_t g = nullptr;
+        check(mqvs_index_group_create(hs.data(), static_cast<int32_t>(hs.size()), &g));
+        group = std::make_shared<GroupHandle>(g, true);
+        nparts = static_cast<int32_t>(hs.size());
+        code_bytes = indexes[0]->segment().codeBytes();
+    }
+
+    int32_t parts() const { return nparts; }
+    int32_t codeBytes() const { return code_bytes; }
+    mqvs_index_group_t handle() const { return group->h; }
+
+    /// The CPU path the call replaces: the per-part index searches and the
+    /// cross-part merge, same arguments and outputs.
+    using GroupFallback = std::function<void(const uint8_t * queries, int32_t nq, int32_t k,
+                                             const std::string & params, const uint8_t * const * filters,
+                                             const uint8_t * const * row_exists, int32_t * part, int64_t * ids,
+                                             float * dist)>;
+
+    /// Raw merged top-k: part / ids / dist nq*k (caller-owned), ascending by
+    /// (distance, part, position); padding slots hold part -1, id -1, FLT_MAX.
+    /// params: alpha / nprobe / metric (num_reorder is accepted and ignored);
+    /// an explicit nprobe is cut to each part's list count.  filters /
+    /// row_exists: nparts bitmap pointers (either array, and any entry, may be
+    /// nullptr).  fallback: runs instead when the device fails (isFallbackStatus).
+    void search(const uint8_t * queries, int32_t nq, int32_t k, const std::string & params,
+                const uint8_t * const * filters, const uint8_t * const * row_exists, int32_t * part, int64_t * ids,
+                float * dist, uint32_t flags = 0, const GroupFallback & fallback = nullptr) const
+    {
+        const int st = mqvs_index_group_search_binary(group->h, queries, nq, k, params.c_str(), filters, row_exists,
+                                                      part, ids, dist, flags, nullptr);
+        checkOrFallback(st, static_cast<bool>(fallback),
+                        [&] { fallback(queries, nq, k, params, filters, row_exists, part, ids, dist); });
+    }
+
+    /// The labelled rows of the merged result, after the reference's check of
+    /// the query's FixedString length.
+    PartRows search(const uint8_t * queries, int32_t nq, int32_t query_bytes, int32_t k, const std::string & params,
+                    const uint8_t * const * filters = nullptr, const uint8_t * const * row_exists = nullptr,
+                    const GroupFallback & fallback = nullptr) const
+    {
+        if (query_bytes != code_bytes)
+            throw DB::Exception(DB::ErrorCodes::LOGICAL_ERROR, "{}",
+                                std::string("The dimension of searched index and input doesn't match."));
+        std::vector<int32_t> part(static_cast<size_t>(nq) * k);
+        std::vector<int64_t> ids(part.size());
+        std::vector<float> dist(part.size());
+        search(queries, nq, k, params, filters, row_exists, part.data(), ids.data(), dist.data(), 0, fallback);
+        PartRows out;
+        for (size_t i = 0; i < ids.size(); ++i)
+        {
+            if (ids[i] <= -1)
+                continue;
+            out.part.push_back(static_cast<uint32_t>(part[i]));
+            out.label.push_back(static_cast<uint32_t>(ids[i]));
+            out.vector_id.push_back(static_cast<uint32_t>(i / static_cast<size_t>(k)));
+            out.distance.push_back(dist[i]);
+        }
+        return out;
+    }
+
+    /// The calling thread's last search (mqvs_index_group_last_stats).
+    static mqvs_index_group_stats lastStats()
+    {
+        mqvs_index_group_stats st{};
+        check(mqvs_index_group_last_stats(&st));
+        return st;
+    }
+
+private:
+    using GroupHandle = Handle<mqvs_index_group_t, mqvs_index_group_free>;
+    std::shared_ptr<GroupHandle> group;
+    int32_t nparts = 0;
+    int32_t code_bytes = 0;
+};
+
 }

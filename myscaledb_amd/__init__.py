@@ -19,6 +19,7 @@ from .vector_scan import (  # noqa: F401
 from .vector_index import BinaryVectorIndex, VectorIndex, index_blob_info  # noqa: F401
 from .part_group import (BinaryPartGroup, PartGroup, part_group_batch, set_part_group_batch,  # noqa: F401
                          set_part_group_binary_rows, set_part_group_rows)
+from .index_group import BinaryIndexGroup  # noqa: F401
 
-__all__ = ["PartGroup", "BinaryPartGroup", "set_part_group_binary_rows", "set_part_group_rows", "set_part_group_batch", "part_group_batch", "index_blob_info","BinaryVectorScanSegment", "try_brute_force_search_binary", "VectorScanSegment", "init", "merge_shards", "pack_bitmap",
+__all__ = ["PartGroup", "BinaryPartGroup", "BinaryIndexGroup", "set_part_group_binary_rows", "set_part_group_rows", "set_part_group_batch", "part_group_batch", "index_blob_info","BinaryVectorScanSegment", "try_brute_force_search_binary", "VectorScanSegment", "init", "merge_shards", "pack_bitmap",
            "try_brute_force_search", "vector_scan_without_index", "VectorIndex", "BinaryVectorIndex"]

@@ -64,6 +64,8 @@ SYMBOLS = [
     "mqvs_part_group_create", "mqvs_part_group_free", "mqvs_part_group_info", "mqvs_part_group_search",
     "mqvs_part_group_last_stats", "mqvs_set_part_group_rows", "mqvs_set_part_group_batch", "mqvs_part_group_batch",
     "mqvs_part_group_search_binary", "mqvs_set_part_group_binary_rows",
+    "mqvs_index_group_create", "mqvs_index_group_free", "mqvs_index_group_info", "mqvs_index_group_search_binary",
+    "mqvs_index_group_last_stats",
 ]
 
 
@@ -87,6 +89,14 @@ class PartGroupStats(ctypes.Structure):
                 ("looped_parts", ctypes.c_int32), ("launches", ctypes.c_int32),
                 ("redo", ctypes.c_int32), ("nq", ctypes.c_int32), ("k", ctypes.c_int32),
                 ("batch", ctypes.c_int32)]
+
+
+class IndexGroupStats(ctypes.Structure):
+    _fields_ = [("total_ms", ctypes.c_double), ("values", ctypes.c_int64), ("items", ctypes.c_int64),
+                ("plane_bytes", ctypes.c_int64), ("pairs", ctypes.c_int64),
+                ("parts", ctypes.c_int32), ("fused_parts", ctypes.c_int32),
+                ("looped_parts", ctypes.c_int32), ("launches", ctypes.c_int32),
+                ("nq", ctypes.c_int32), ("k", ctypes.c_int32)]
 
 
 class IndexInfo(ctypes.Structure):
@@ -228,6 +238,11 @@ def _load(path=LIB_PATH):
         "mqvs_part_group_batch": ([P, P], ctypes.c_int),
         "mqvs_part_group_search_binary": ([P, P, I32, I32, I32, P, P, P, P, P, U32, P], ctypes.c_int),
         "mqvs_set_part_group_binary_rows": ([I64], I64),
+        "mqvs_index_group_create": ([P, I32, P], ctypes.c_int),
+        "mqvs_index_group_free": ([P], ctypes.c_int),
+        "mqvs_index_group_info": ([P, P, P, P, P, P], ctypes.c_int),
+        "mqvs_index_group_search_binary": ([P, P, I32, I32, ctypes.c_char_p, P, P, P, P, P, U32, P], ctypes.c_int),
+        "mqvs_index_group_last_stats": ([P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

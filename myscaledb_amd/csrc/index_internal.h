@@ -214,6 +214,18 @@ void index_collect_stats(int device);
 void search_binary_index_impl(mqvs_index *ix, const uint8_t *queries, int nq, int k, const char *params,
                               const uint8_t *filter, const uint8_t *exists, int64_t *out_ids, float *out_dist,
                               uint32_t flags, hipStream_t user_stream, int64_t *probes_out);
+// with the search parameters resolved (metric Hamming or Jaccard, 1 <= nprobe <= nlist)
+void search_binary_index_impl(mqvs_index *ix, const uint8_t *queries, int nq, int k, int metric, int nprobe,
+                              const uint8_t *filter, const uint8_t *exists, int64_t *out_ids, float *out_dist,
+                              uint32_t flags, hipStream_t user_stream, int64_t *probes_out);
+// a query's record region of a binary index search: at most every position of its probed lists
+inline int64_t binary_index_cap(const mqvs_index *ix, int nprobe) {
+    return std::max<int64_t>(1, std::min<int64_t>((int64_t)nprobe * ix->max_list, ix->npos));
+}
+// a query's scratch bytes of one: its records, and its centroid distances when the lists are ranked
+inline int64_t binary_index_scratch(const mqvs_index *ix, int nprobe) {
+    return binary_index_cap(ix, nprobe) * (int64_t)sizeof(Cand) + (nprobe < ix->nlist ? ix->nlist * 4 : 0);
+}
 
 // ---- index_blob.hip
 size_t blob_bytes(const mqvs_index *ix);

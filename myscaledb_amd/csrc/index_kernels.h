@@ -29,8 +29,9 @@
 //   kernels_ivf_select.hip  k_ivf_select, k_ivf_select_small
 //   kernels_ivf_pick.hip    k_coarse_pick (the coarse step's exact pick)
 //   kernels_ivf_build.hip   k_ivf_pack, k_to_fp8, k_gather_rows, k_centroid_mean, k_grp_*
-//   kernels_bivf.hip        the binary index: k_bivf_*
-// Included by index_internal.h (the host files) and those six files only.
+//   kernels_bivf.hip        the binary index: k_bivf_*, and k_bivf_group_* (index groups)
+//   kernels_select.hip      k_bivf_group_select (the final select's body per (slot, query))
+// Included by index_internal.h (the host files) and those seven files only.
 #pragma once
 
 #include "mqvs_internal.h"
@@ -206,5 +207,53 @@ void launch_bivf_coarse(const uint32_t *cent, int nlist, int code_words, const u
                         uint32_t *cdist, int64_t *probes, hipStream_t s);
 // metric: Hamming or Jaccard; stats (optional): [4] values, items, plane bytes, pairs
 void launch_bivf_scan(const BivfParams &p, int metric, int64_t *stats, hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// Binary index groups (index_group.hip): one slot per fused part of a grouped
+// launch chain.  A slice's table of m slots ends with a sentinel (part -1)
+// whose prefix sums are the slice's totals.  cent0 / ctile0 / item0 / cand0
+// restart in every slice (the centroid-distance matrix and the records are the
+// slice's scratch); probe0 / count0 run over the whole call, whose probes and
+// record counts stay for the stats kernel.
+struct BivfGroupSlot {
+    const uint32_t *bcent;        // [nlist][code_words] the part's centroids
+    const uint32_t *bplane;       // [npos][code_words] codes in list order
+    const int32_t *perm;          // [npos] part row of each position
+    const int64_t *list_off;      // [nlist+1]
+    const uint8_t *filter;        // this call's PREWHERE bitmap of the part, or null
+    const uint8_t *exists;        // this call's lightweight-delete bitmap, or null
+    const uint64_t *row_ids_map;  // the part's row-ids map (decoupled part), or null
+    int64_t row_offset;
+    int64_t cent0;                // the part's column in the [nq][sum nlist] distance matrix (ranked slots)
+    int64_t ctile0;               // centroid tiles, nq * ceil(nlist / 256) per ranked slot
+    int64_t probe0;               // probes, nq * nprobe per slot: probes[probe0 + q * nprobe + r]
+    int64_t item0;                // scan work items, nq * nprobe * nch per slot
+    int64_t cand0;                // records, nq * cap per slot: region (slot, q) at cand0 + q * cap
+    int64_t count0;               // record counters, nq per slot
+    int32_t nlist;
+    int32_t nprobe;               // == nlist: every list in order, no ranking
+    int32_t nch;                  // ceil(longest list / 256)
+    int32_t cap;                  // records per (slot, query) region: every position of the probed lists
+    int32_t part;                 // position in the group (the merge's list index); -1: the sentinel
+    int32_t pad;
+};
+// cdist: the slice's [nq][ld] words (ld = the sentinel's cent0, ctiles its
+// ctile0); also zeroes the slots' record counters
+void launch_bivf_group_coarse(const BivfGroupSlot *slots, int nslots, int64_t ctiles, int code_words,
+                              const uint32_t *qcodes, int nq, uint32_t *cdist, int64_t ld, int64_t *probes, int *count,
+                              hipStream_t s);
+// base: code_words, nbits, nq, qcodes, probes, cand set; the per-part fields come from the slots
+void launch_bivf_group_scan(const BivfParams &base, const BivfGroupSlot *slots, int nslots, int64_t items, int *count,
+                            int metric, hipStream_t s);
+// kernels_select.hip: per (slot, query) the k best records of the region by
+// (distance, part row) -> list_ids / list_dist [group parts][nq][k] at the slot's part
+void launch_bivf_group_select(const Cand *cand, const int *count, const BivfGroupSlot *slots, int nslots, int nq,
+                              int k, int64_t *list_ids, float *list_dist, int *overflow, hipStream_t s);
+// over all nentries table entries of the call (sentinels included, skipped)
+void launch_bivf_group_map(const BivfGroupSlot *slots, int nentries, int64_t per_part, int64_t *list_ids,
+                           hipStream_t s);
+// stats[4] (zeroed) += values, items, plane bytes, pairs of every slot
+void launch_bivf_group_stats(const BivfGroupSlot *slots, int nentries, int nq, int code_words, const int64_t *probes,
+                             const int *count, int64_t *stats, hipStream_t s);
 
 }  // namespace mqvs

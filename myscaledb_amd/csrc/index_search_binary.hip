@@ -186,6 +186,15 @@ void search_binary_index_impl(mqvs_index *ix, const uint8_t *queries, int nq, in
     const int nprobe = search_nprobe(ix, pm);
     // (accepted and ignored: the scan is exact, nothing is re-ordered)
     (void)num_param(pm, "num_reorder", 1, 1, (double)kLargeCap);
+    search_binary_index_impl(ix, queries, nq, k, metric, nprobe, filter, exists, out_ids, out_dist, flags, user_stream,
+                             probes_out);
+}
+
+// The same with the search parameters resolved (the driver above; an index
+// group's per-part route): metric Hamming or Jaccard, 1 <= nprobe <= nlist.
+void search_binary_index_impl(mqvs_index *ix, const uint8_t *queries, int nq, int k, int metric, int nprobe,
+                              const uint8_t *filter, const uint8_t *exists, int64_t *out_ids, float *out_dist,
+                              uint32_t flags, hipStream_t user_stream, int64_t *probes_out) {
     mqvs_index_search_stats st{};
     st.nq = nq;
     st.k = k;
@@ -195,16 +204,15 @@ void search_binary_index_impl(mqvs_index *ix, const uint8_t *queries, int nq, in
 
     mqvs_segment *seg = ix->seg;
     // a query's records: at most every position of its probed lists
-    const int64_t cap = std::max<int64_t>(1, std::min<int64_t>((int64_t)nprobe * ix->max_list, ix->npos));
+    const int64_t cap = binary_index_cap(ix, nprobe);
     // query sub-batches under the scratch budget (records, centroid
     // distances, the large-k sort scratch); the stats are the sub-batches' sums
-    const int64_t perq = cap * (int64_t)sizeof(Cand) + (nprobe < ix->nlist ? ix->nlist * 4 : 0) +
-                         (k > kSortCap ? (int64_t)sizeof(uint4) * 2 * kLargeCap : 0);
+    const int64_t perq = binary_index_scratch(ix, nprobe) + (k > kSortCap ? (int64_t)sizeof(uint4) * 2 * kLargeCap : 0);
     const int qb = (int)std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)scratch_budget() / perq));
     if (nq > qb) {
         mqvs_index_search_stats sum = st;
         for_query_batches(nq, qb, [&](int q0, int m) {
-            search_binary_index_impl(ix, queries + (size_t)q0 * seg->code_bytes, m, k, params, filter, exists,
+            search_binary_index_impl(ix, queries + (size_t)q0 * seg->code_bytes, m, k, metric, nprobe, filter, exists,
                                      out_ids + (size_t)q0 * k, out_dist + (size_t)q0 * k, flags, user_stream,
                                      probes_out ? probes_out + (size_t)q0 * nprobe : nullptr);
             sum.coarse_ms += g_istats.coarse_ms;

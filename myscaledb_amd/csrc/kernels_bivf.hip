@@ -168,6 +168,15 @@ void launch_bivf_gather(const uint32_t *src, int code_words, const int32_t *idx,
 
 // ---- coarse -----------------------------------------------------------------
 
+// the Hamming distance of query row qq and centroid row cc ([W4] 16-B slices)
+__device__ __forceinline__ uint32_t bivf_cdist_one(const uint32_t *qq, const uint32_t *cc, int W4) {
+    const bivf_u32x4 *c4 = reinterpret_cast<const bivf_u32x4 *>(cc);
+    const bivf_u32x4 *q4 = reinterpret_cast<const bivf_u32x4 *>(qq);
+    uint32_t a = 0;
+    for (int u = 0; u < W4; ++u) a += pop_xor(q4[u], c4[u]);
+    return a;
+}
+
 __global__ __launch_bounds__(256) void k_bivf_cdist(const uint32_t *cent, int nlist, int code_words,
                                                     const uint32_t *qcodes, int nq, uint32_t *out) {
     const int W4 = code_words / 4;
@@ -177,23 +186,18 @@ __global__ __launch_bounds__(256) void k_bivf_cdist(const uint32_t *cent, int nl
         const int q = (int)(ti / tpq);
         const int c = (int)(ti % tpq) * 256 + threadIdx.x;
         if (c >= nlist) continue;
-        const bivf_u32x4 *cc = reinterpret_cast<const bivf_u32x4 *>(cent + (int64_t)c * code_words);
-        const bivf_u32x4 *qq = reinterpret_cast<const bivf_u32x4 *>(qcodes + (int64_t)q * code_words);
-        uint32_t a = 0;
-        for (int u = 0; u < W4; ++u) a += pop_xor(qq[u], cc[u]);
-        out[(int64_t)q * nlist + c] = a;
+        out[(int64_t)q * nlist + c] =
+            bivf_cdist_one(qcodes + (int64_t)q * code_words, cent + (int64_t)c * code_words, W4);
     }
 }
 
-// probes[q][0, nprobe) = the nprobe lists of smallest (distance, list id), in
-// no particular order; nprobe < nlist
-__global__ __launch_bounds__(SEL_THREADS) void k_bivf_pick(const uint32_t *cdist, int nlist, int nprobe,
-                                                           int64_t *probes) {
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t sh[4];
-    __shared__ int s_cnt;
-    const int q = blockIdx.x;
-    const uint32_t *d = cdist + (int64_t)q * nlist;
+// out[0, nprobe) = the nprobe lists of smallest (distance, list id) among
+// d[0, nlist), in no particular order; nprobe < nlist.  The whole workgroup
+// calls it (k_bivf_pick and the grouped pick: the rule is stated once).
+// hist[256], sh[4], s_cnt_p: LDS words.
+__device__ __forceinline__ void bivf_pick_body(const uint32_t *d, int nlist, int nprobe, int64_t *out, uint32_t *hist,
+                                               uint32_t *sh, int *s_cnt_p) {
+    int &s_cnt = *s_cnt_p;
     const uint32_t th = block_radix_select_mlp([&](int64_t i) { return d[i]; }, nlist, nprobe, hist, sh);
     if (threadIdx.x == 0) s_cnt = 0;
     __syncthreads();
@@ -211,9 +215,20 @@ __global__ __launch_bounds__(SEL_THREADS) void k_bivf_pick(const uint32_t *cdist
         const uint32_t v = d[i];
         if (v < th || (v == th && (uint32_t)i <= lth)) {
             const int slot = atomicAdd(&s_cnt, 1);
-            if (slot < nprobe) probes[(int64_t)q * nprobe + slot] = i;
+            if (slot < nprobe) out[slot] = i;
         }
     }
+}
+
+// probes[q][0, nprobe) = the nprobe lists of smallest (distance, list id), in
+// no particular order; nprobe < nlist
+__global__ __launch_bounds__(SEL_THREADS) void k_bivf_pick(const uint32_t *cdist, int nlist, int nprobe,
+                                                           int64_t *probes) {
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t sh[4];
+    __shared__ int s_cnt;
+    const int q = blockIdx.x;
+    bivf_pick_body(cdist + (int64_t)q * nlist, nlist, nprobe, probes + (int64_t)q * nprobe, hist, sh, &s_cnt);
 }
 
 void launch_bivf_coarse(const uint32_t *cent, int nlist, int code_words, const uint32_t *qcodes, int nq, int nprobe,
@@ -271,64 +286,67 @@ __device__ inline void bivf_emit(const BivfParams &p, int q, bool lead, int64_t 
 // partial popcounts are combined by xor-shuffles.  W4 = 0: a position per
 // lane (rows of other widths), the query's slices wave-uniform.
 template <int METRIC, int W4>
-__global__ __launch_bounds__(256) void k_bivf_scan(BivfParams p) {
+__device__ __forceinline__ void bivf_scan_item(const BivfParams &p, int q, int64_t list, int ch) {
     const int t = threadIdx.x;
-    const int64_t items = (int64_t)p.nq * p.nprobe * p.nch;
     const bivf_u32x4 *plane = reinterpret_cast<const bivf_u32x4 *>(p.plane);
+    if (list < 0 || list >= p.nlist) return;  // (block-uniform)
+    const int64_t b0 = p.list_off[list] + (int64_t)ch * 256, le = p.list_off[list + 1];
+    if (b0 >= le) return;
+    const int64_t e0 = le < b0 + 256 ? le : b0 + 256;
+    if (W4 > 0) {
+        const int u = t & (W4 - 1);
+        const bivf_u32x4 qv = reinterpret_cast<const bivf_u32x4 *>(p.qcodes + (int64_t)q * p.code_words)[u];
+        bivf_u32x4 y[W4 > 0 ? W4 : 1];
+#pragma unroll
+        for (int sidx = 0; sidx < W4; ++sidx) {
+            const int idx = sidx * 256 + t;
+            const int64_t pos = b0 + idx / W4;
+            y[sidx] = pos < e0 ? __builtin_nontemporal_load(plane + b0 * W4 + idx) : bivf_u32x4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (int sidx = 0; sidx < W4; ++sidx) {
+            const int64_t pos = b0 + (sidx * 256 + t) / W4;
+            uint32_t a, b = 0u;
+            if (METRIC == MQVS_METRIC_HAMMING) {
+                a = pop_xor(qv, y[sidx]);
+            } else {
+                a = pop_and(qv, y[sidx]);
+                b = pop_or(qv, y[sidx]);
+            }
+#pragma unroll
+            for (int o = 1; o < W4; o <<= 1) {
+                a += __shfl_xor(a, o);
+                if (METRIC == MQVS_METRIC_JACCARD) b += __shfl_xor(b, o);
+            }
+            bivf_emit<METRIC>(p, q, u == 0 && pos < e0, pos, a, b);
+        }
+    } else {
+        const int W = p.code_words / 4;
+        const int64_t pos = b0 + t;
+        const bool in = pos < e0;
+        const bivf_u32x4 *yr = plane + (in ? pos : b0) * W;
+        const bivf_u32x4 *qr = reinterpret_cast<const bivf_u32x4 *>(p.qcodes + (int64_t)q * p.code_words);
+        uint32_t a = 0u, b = 0u;
+        for (int u = 0; u < W; ++u) {
+            const bivf_u32x4 yy = __builtin_nontemporal_load(yr + u), qq = qr[u];
+            if (METRIC == MQVS_METRIC_HAMMING) {
+                a += pop_xor(qq, yy);
+            } else {
+                a += pop_and(qq, yy);
+                b += pop_or(qq, yy);
+            }
+        }
+        bivf_emit<METRIC>(p, q, in, pos, a, b);
+    }
+}
+
+template <int METRIC, int W4>
+__global__ __launch_bounds__(256) void k_bivf_scan(BivfParams p) {
+    const int64_t items = (int64_t)p.nq * p.nprobe * p.nch;
     for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
         const int ch = (int)(it % p.nch);
         const int64_t pair = it / p.nch;
-        const int q = (int)(pair / p.nprobe);
-        const int64_t list = p.probes[pair];
-        if (list < 0 || list >= p.nlist) continue;  // (block-uniform)
-        const int64_t b0 = p.list_off[list] + (int64_t)ch * 256, le = p.list_off[list + 1];
-        if (b0 >= le) continue;
-        const int64_t e0 = le < b0 + 256 ? le : b0 + 256;
-        if (W4 > 0) {
-            const int u = t & (W4 - 1);
-            const bivf_u32x4 qv = reinterpret_cast<const bivf_u32x4 *>(p.qcodes + (int64_t)q * p.code_words)[u];
-            bivf_u32x4 y[W4 > 0 ? W4 : 1];
-#pragma unroll
-            for (int sidx = 0; sidx < W4; ++sidx) {
-                const int idx = sidx * 256 + t;
-                const int64_t pos = b0 + idx / W4;
-                y[sidx] = pos < e0 ? __builtin_nontemporal_load(plane + b0 * W4 + idx) : bivf_u32x4{0u, 0u, 0u, 0u};
-            }
-#pragma unroll
-            for (int sidx = 0; sidx < W4; ++sidx) {
-                const int64_t pos = b0 + (sidx * 256 + t) / W4;
-                uint32_t a, b = 0u;
-                if (METRIC == MQVS_METRIC_HAMMING) {
-                    a = pop_xor(qv, y[sidx]);
-                } else {
-                    a = pop_and(qv, y[sidx]);
-                    b = pop_or(qv, y[sidx]);
-                }
-#pragma unroll
-                for (int o = 1; o < W4; o <<= 1) {
-                    a += __shfl_xor(a, o);
-                    if (METRIC == MQVS_METRIC_JACCARD) b += __shfl_xor(b, o);
-                }
-                bivf_emit<METRIC>(p, q, u == 0 && pos < e0, pos, a, b);
-            }
-        } else {
-            const int W = p.code_words / 4;
-            const int64_t pos = b0 + t;
-            const bool in = pos < e0;
-            const bivf_u32x4 *yr = plane + (in ? pos : b0) * W;
-            const bivf_u32x4 *qr = reinterpret_cast<const bivf_u32x4 *>(p.qcodes + (int64_t)q * p.code_words);
-            uint32_t a = 0u, b = 0u;
-            for (int u = 0; u < W; ++u) {
-                const bivf_u32x4 yy = __builtin_nontemporal_load(yr + u), qq = qr[u];
-                if (METRIC == MQVS_METRIC_HAMMING) {
-                    a += pop_xor(qq, yy);
-                } else {
-                    a += pop_and(qq, yy);
-                    b += pop_or(qq, yy);
-                }
-            }
-            bivf_emit<METRIC>(p, q, in, pos, a, b);
-        }
+        bivf_scan_item<METRIC, W4>(p, (int)(pair / p.nprobe), p.probes[pair], ch);
     }
 }
 
@@ -381,6 +399,184 @@ void launch_bivf_scan(const BivfParams &p, int metric, int64_t *stats, hipStream
             bivf_scan_t<MQVS_METRIC_JACCARD>(p, grid, s);
     }
     if (stats) hipLaunchKernelGGL(k_bivf_stats, dim3(1), dim3(256), 0, s, p, stats);
+}
+
+// ---- index groups (index_group.hip) -------------------------------------------
+// The search kernels above with a batch dimension over the indexed parts of a
+// group: one slot per part (BivfGroupSlot, index_kernels.h).  A workgroup's
+// work unit v belongs to the last slot whose prefix sum (ctile0 / item0) is
+// <= v -- the table ends with a sentinel holding the totals, and slots without
+// units are skipped -- which depends on blockIdx only, so it is wave-uniform.
+__device__ __forceinline__ int bivf_group_slot(const BivfGroupSlot *slots, int nslots, int64_t v,
+                                               int64_t BivfGroupSlot::*key) {
+    int lo = 0, hi = nslots;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (slots[mid].*key <= v) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// k_bivf_cdist over the 256-centroid tiles of every (ranked slot, query):
+// cdist[q][cent0 + c] of the slice's [nq][ld] matrix
+__global__ __launch_bounds__(256) void k_bivf_group_cdist(const BivfGroupSlot *slots, int nslots, int64_t tiles,
+                                                          int code_words, const uint32_t *qcodes, uint32_t *cdist,
+                                                          int64_t ld) {
+    const int W4 = code_words / 4;
+    for (int64_t ti = blockIdx.x; ti < tiles; ti += gridDim.x) {
+        const BivfGroupSlot &g = slots[bivf_group_slot(slots, nslots, ti, &BivfGroupSlot::ctile0)];
+        const int64_t local = ti - g.ctile0;
+        const int64_t tpq = (g.nlist + 255) / 256;
+        const int q = (int)(local / tpq);
+        const int c = (int)(local % tpq) * 256 + threadIdx.x;
+        if (c >= g.nlist) continue;
+        cdist[(int64_t)q * ld + g.cent0 + c] =
+            bivf_cdist_one(qcodes + (int64_t)q * code_words, g.bcent + (int64_t)c * code_words, W4);
+    }
+}
+
+// workgroup (slot, query): the slot's probes of the query -- k_bivf_pick's
+// rule over the slot's columns, or every list in order when the slot probes
+// all of them -- and the (slot, query) record counter zeroed for the scan
+__global__ __launch_bounds__(SEL_THREADS) void k_bivf_group_pick(const BivfGroupSlot *slots, int nq,
+                                                                 const uint32_t *cdist, int64_t ld, int64_t *probes,
+                                                                 int *count) {
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t sh[4];
+    __shared__ int s_cnt;
+    const int q = blockIdx.x % nq;
+    const BivfGroupSlot &g = slots[blockIdx.x / nq];
+    int64_t *out = probes + g.probe0 + (int64_t)q * g.nprobe;
+    if (threadIdx.x == 0) count[g.count0 + q] = 0;
+    if (g.nprobe < g.nlist) {  // (block-uniform)
+        bivf_pick_body(cdist + (int64_t)q * ld + g.cent0, g.nlist, g.nprobe, out, hist, sh, &s_cnt);
+    } else {
+        for (int r = threadIdx.x; r < g.nprobe; r += SEL_THREADS) out[r] = r;
+    }
+}
+
+// k_bivf_scan's work items of every slot: item it of the launch is (query,
+// probe, 256-position slice) it - item0 of its slot; the records go to the
+// (slot, query) region cand[cand0 + q cap ..) under count[count0 + q]
+template <int METRIC, int W4>
+__global__ __launch_bounds__(256) void k_bivf_group_scan(BivfParams base, const BivfGroupSlot *slots, int nslots,
+                                                         int64_t items, int *count) {
+    for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+        const BivfGroupSlot &g = slots[bivf_group_slot(slots, nslots, it, &BivfGroupSlot::item0)];
+        const int64_t local = it - g.item0;
+        const int ch = (int)(local % g.nch);
+        const int64_t pair = local / g.nch;
+        BivfParams p = base;
+        p.plane = g.bplane;
+        p.perm = g.perm;
+        p.list_off = g.list_off;
+        p.nlist = g.nlist;
+        p.filter = g.filter;
+        p.exists = g.exists;
+        p.cand = base.cand + g.cand0;
+        p.cand_count = count + g.count0;
+        p.cand_cap = g.cap;
+        bivf_scan_item<METRIC, W4>(p, (int)(pair / g.nprobe), base.probes[g.probe0 + pair], ch);
+    }
+}
+
+template <int METRIC>
+static void bivf_group_scan_t(const BivfParams &p, const BivfGroupSlot *slots, int nslots, int64_t items, int *count,
+                              int grid, hipStream_t s) {
+#define MQVS_BIVF_GROUP_SCAN(W)                                                                                 \
+    hipLaunchKernelGGL((k_bivf_group_scan<METRIC, W>), dim3(grid), dim3(256), 0, s, p, slots, nslots, items, count)
+    switch (p.code_words / 4) {
+        case 1: MQVS_BIVF_GROUP_SCAN(1); return;
+        case 2: MQVS_BIVF_GROUP_SCAN(2); return;
+        case 4: MQVS_BIVF_GROUP_SCAN(4); return;
+        case 8: MQVS_BIVF_GROUP_SCAN(8); return;
+        default: MQVS_BIVF_GROUP_SCAN(0); return;
+    }
+#undef MQVS_BIVF_GROUP_SCAN
+}
+
+void launch_bivf_group_coarse(const BivfGroupSlot *slots, int nslots, int64_t ctiles, int code_words,
+                              const uint32_t *qcodes, int nq, uint32_t *cdist, int64_t ld, int64_t *probes, int *count,
+                              hipStream_t s) {
+    if (nq <= 0 || nslots <= 0) return;
+    if (ctiles > 0)
+        hipLaunchKernelGGL(k_bivf_group_cdist, dim3((unsigned)std::min<int64_t>(ctiles, 1 << 20)), dim3(256), 0, s,
+                           slots, nslots, ctiles, code_words, qcodes, cdist, ld);
+    hipLaunchKernelGGL(k_bivf_group_pick, dim3((unsigned)nslots * nq), dim3(SEL_THREADS), 0, s, slots, nq, cdist, ld,
+                       probes, count);
+}
+
+void launch_bivf_group_scan(const BivfParams &base, const BivfGroupSlot *slots, int nslots, int64_t items, int *count,
+                            int metric, hipStream_t s) {
+    if (items <= 0 || nslots <= 0) return;
+    const int grid = (int)std::min<int64_t>(items, 1 << 16);
+    if (metric == MQVS_METRIC_HAMMING)
+        bivf_group_scan_t<MQVS_METRIC_HAMMING>(base, slots, nslots, items, count, grid, s);
+    else
+        bivf_group_scan_t<MQVS_METRIC_JACCARD>(base, slots, nslots, items, count, grid, s);
+}
+
+// workgroup (table entry, one of bx blocks over the entry's nq * k results):
+// ids through the part's row-ids map, as k_map_ids; slots without a map (and
+// sentinels) return
+__global__ __launch_bounds__(256) void k_bivf_group_map(const BivfGroupSlot *slots, int bx, int64_t per_part,
+                                                        int64_t *list_ids) {
+    const BivfGroupSlot &g = slots[blockIdx.x / bx];
+    if (g.part < 0 || !g.row_ids_map) return;
+    int64_t *ids = list_ids + (int64_t)g.part * per_part;
+    for (int64_t i = (blockIdx.x % bx) * 256ll + threadIdx.x; i < per_part; i += (int64_t)bx * 256) {
+        const int64_t v = ids[i];
+        if (v >= 0) ids[i] = (int64_t)g.row_ids_map[v];
+    }
+}
+
+void launch_bivf_group_map(const BivfGroupSlot *slots, int nentries, int64_t per_part, int64_t *list_ids,
+                           hipStream_t s) {
+    if (nentries <= 0 || per_part <= 0) return;
+    const int bx = (int)std::min<int64_t>((per_part + 255) / 256, 64);
+    hipLaunchKernelGGL(k_bivf_group_map, dim3((unsigned)nentries * bx), dim3(256), 0, s, slots, bx, per_part,
+                       list_ids);
+}
+
+// k_bivf_stats' four sums over every slot of the call (workgroup = table
+// entry; stats[4] zeroed by the caller): records kept, non-empty work items,
+// list-plane bytes of the probed lists, (query, list) pairs
+__global__ __launch_bounds__(256) void k_bivf_group_stats(const BivfGroupSlot *slots, int nq, int code_words,
+                                                          const int64_t *probes, const int *count,
+                                                          unsigned long long *stats) {
+    __shared__ unsigned long long acc[3];
+    const BivfGroupSlot &g = slots[blockIdx.x];
+    if (g.part < 0) return;  // (a sentinel; block-uniform)
+    if (threadIdx.x < 3) acc[threadIdx.x] = 0ull;
+    __syncthreads();
+    unsigned long long vals = 0, items = 0, pos = 0;
+    for (int i = threadIdx.x; i < nq; i += 256) vals += (unsigned long long)count[g.count0 + i];
+    const int64_t E = (int64_t)nq * g.nprobe;
+    for (int64_t e = threadIdx.x; e < E; e += 256) {
+        const int64_t list = probes[g.probe0 + e];
+        if (list < 0 || list >= g.nlist) continue;
+        const int64_t len = g.list_off[list + 1] - g.list_off[list];
+        pos += (unsigned long long)len;
+        items += (unsigned long long)((len + 255) / 256);
+    }
+    atomicAdd(&acc[0], vals);
+    atomicAdd(&acc[1], items);
+    atomicAdd(&acc[2], pos);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&stats[0], acc[0]);
+        atomicAdd(&stats[1], acc[1]);
+        atomicAdd(&stats[2], acc[2] * (unsigned long long)code_words * 4ull);
+        atomicAdd(&stats[3], (unsigned long long)E);
+    }
+}
+
+void launch_bivf_group_stats(const BivfGroupSlot *slots, int nentries, int nq, int code_words, const int64_t *probes,
+                             const int *count, int64_t *stats, hipStream_t s) {
+    if (nentries <= 0 || nq <= 0) return;
+    hipLaunchKernelGGL(k_bivf_group_stats, dim3((unsigned)nentries), dim3(256), 0, s, slots, nq, code_words, probes,
+                       count, reinterpret_cast<unsigned long long *>(stats));
 }
 
 }  // namespace mqvs

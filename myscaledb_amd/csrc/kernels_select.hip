@@ -13,6 +13,7 @@
 //                   (L2/IP: key, row; cosine: 1-ip, chunk, ip desc, row) and
 //                   emit the first k in the reference's output layout.
 
+#include "index_kernels.h"
 #include "select_common.h"
 
 namespace mqvs {
@@ -282,6 +283,30 @@ __global__ __launch_bounds__(SEL_THREADS) void k_select_group(const float *matri
                               (uint4 *)nullptr, recs, hist, sh, &s_cnt);
 }
 
+// Index-group select (index_group.hip): workgroup (slot, query) runs the final
+// select over the (slot, query) region of the grouped list scan's records, in
+// the L2 order (binary distances: ascending finite values, (key, row) ties) --
+// what k_final_select does for mqvs_index_search_binary's one part.
+__global__ __launch_bounds__(SEL_THREADS) void k_bivf_group_select(const Cand *cand, const int *count,
+                                                                  const BivfGroupSlot *slots, int nq, int k,
+                                                                  int64_t *list_ids, float *list_dist,
+                                                                  int *overflow) {
+    extern __shared__ __attribute__((aligned(16))) uint4 recs[];  // kSortCap records
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t sh[4];
+    __shared__ int s_cnt;
+    const int q = blockIdx.x % nq;
+    const BivfGroupSlot &g = slots[blockIdx.x / nq];
+    int n = count[g.count0 + q];
+    if (n > g.cap) {
+        if (threadIdx.x == 0) atomicOr(overflow, 1);
+        n = g.cap;
+    }
+    const int64_t o = ((int64_t)g.part * nq + q) * k;
+    final_select_body<MQVS_METRIC_L2>(cand + g.cand0 + (int64_t)q * g.cap, n, k, 0, g.row_offset, list_ids + o,
+                                      list_dist + o, overflow, (uint4 *)nullptr, recs, hist, sh, &s_cnt);
+}
+
 // Merge of per-list results: key (distance, list, position).  rev_ties (IP
 // cross-PART merge, MergeTreeBaseSearchManager.cpp:207-297): the reference
 // walks its insertion-ordered multimap backwards for DESC, so equal scores
@@ -473,6 +498,13 @@ void launch_select_group(const float *matrix, int64_t ld, const GroupSlot *slots
     if (nq <= 0 || nslots <= 0) return;
     MQVS_DISPATCH_METRIC(metric, select_group_t,
                          (matrix, ld, slots, nslots, nq, k, list_ids, list_dist, overflow, s));
+}
+
+void launch_bivf_group_select(const Cand *cand, const int *count, const BivfGroupSlot *slots, int nslots, int nq,
+                              int k, int64_t *list_ids, float *list_dist, int *overflow, hipStream_t s) {
+    if (nq <= 0 || nslots <= 0) return;
+    hipLaunchKernelGGL(k_bivf_group_select, dim3((unsigned)nslots * nq), dim3(SEL_THREADS), sort_lds(kSortCap), s, cand,
+                       count, slots, nq, k, list_ids, list_dist, overflow);
 }
 
 // ---------------------------------------------------------------------------

@@ -29,7 +29,7 @@
 #include <chrono>
 #include <vector>
 
-#include "workspace.h"
+#include "group_call.h"
 
 struct mqvs_part_group {
     std::vector<mqvs_segment *> segs;
@@ -96,155 +96,43 @@ static mqvs_part_group *group_create(const mqvs_segment_t *segs, int nparts) {
     return g;
 }
 
-// 16-B aligned offsets of the staged bitmaps in one buffer
-static size_t bitmap_slot(size_t &total, int64_t n) {
-    const size_t off = total;
-    total += (size_t)round_up((n + 7) / 8, 16);
-    return off;
-}
-
 // slots [first_slot, first_slot + nslots) (+ the sentinel) of one grouped
 // scan + select: fused parts whose dense matrix fits the scratch budget
 struct Slice {
     int first_slot, nslots;
     int64_t tiles, cols;
 };
+using PartGroupCall = GroupCall<GroupSlot, Slice>;
 
-// What the two group searches do the same way around their scans: the slot
-// tables of the fused parts cut into slices, the call's host inputs staged
-// with them in one copy, the per-part lists, and the merge with the call's
-// one host wait.
-struct GroupCall {
-    const mqvs_part_group *g;
-    Workspace &ws;
-    hipStream_t s;
-    bool dev;
-    int nq, k;
-    const uint8_t *const *filters;
-    const uint8_t *const *exists;
-    std::vector<Slice> slices;
-    std::vector<GroupSlot> slots;
-    std::vector<size_t> foff, eoff;
-    const GroupSlot *dslots = nullptr;
-    const uint8_t *dbits = nullptr;
-    const uint8_t *dextra = nullptr;  // stage()'s extra bytes on the device
-    int64_t *list_ids = nullptr;      // [nparts][nq][k]
-    float *list_dist = nullptr;
-    CallIO::Out out{};
-    int32_t *dpart = nullptr;
+static std::vector<int64_t> part_rows(const mqvs_part_group *g) {
+    std::vector<int64_t> rows;
+    for (const mqvs_segment *seg : g->segs) rows.push_back(seg->n);
+    return rows;
+}
 
-    int nparts() const { return (int)g->segs.size(); }
-
-    // fill(p, e) sets the part's own fields of its slot and returns its tiles
-    template <typename Fill>
-    void build_slices(const std::vector<char> &fused, Fill &&fill) {
-        const int64_t max_cols = std::max<int64_t>(1, (int64_t)(scratch_budget() / (sizeof(float) * (size_t)nq)));
-        Slice cur{0, 0, 0, 0};
-        auto close = [&] {
-            if (cur.nslots == 0) return;
-            GroupSlot end{};
-            end.tile0 = cur.tiles;
-            end.col0 = cur.cols;
-            end.part = -1;
-            slots.push_back(end);
-            slices.push_back(cur);
-            cur = Slice{(int)slots.size(), 0, 0, 0};
-        };
-        for (int p = 0; p < nparts(); ++p) {
-            if (!fused[p]) continue;
+// the slices of a call's fused parts: a slice's dense [nq][cols] fp32 matrix
+// fits the scratch budget.  fill(p, e) sets the part's own fields of its slot
+// and returns its tiles
+template <typename Fill>
+static void build_part_slices(PartGroupCall &c, const mqvs_part_group *g, const std::vector<char> &fused, Fill &&fill) {
+    const int64_t max_cols = std::max<int64_t>(1, (int64_t)(scratch_budget() / (sizeof(float) * (size_t)c.nq)));
+    c.build_slices(
+        fused, max_cols, [&](int p) { return g->segs[p]->n; },
+        [&](int p, GroupSlot &e, Slice &cur) {
             const mqvs_segment *seg = g->segs[p];
-            if (cur.nslots > 0 && cur.cols + seg->n > max_cols) close();
-            GroupSlot e{};
             e.n = seg->n;
             e.granule = seg->granule;
             e.row_offset = seg->row_offset;
             e.tile0 = cur.tiles;
             e.col0 = cur.cols;
-            e.part = p;
-            const int64_t tiles = fill(p, e);
-            slots.push_back(e);
-            cur.nslots += 1;
-            cur.tiles += tiles;
+            cur.tiles += fill(p, e);
             cur.cols += seg->n;
-        }
-        close();
-    }
-
-    // this call's bitmaps of part p on the device
-    const uint8_t *part_filter(int p) const {
-        return !(filters && filters[p]) ? nullptr : dev ? filters[p] : dbits + foff[p];
-    }
-    const uint8_t *part_exists(int p) const {
-        return !(exists && exists[p]) ? nullptr : dev ? exists[p] : dbits + eoff[p];
-    }
-
-    // the slot tables, the host bitmaps of every part and `extra` (host bytes
-    // of the call, or null) through one pinned buffer, one copy to the device
-    void stage(const void *extra, size_t extra_bytes) {
-        const int np = nparts();
-        foff.assign(np, (size_t)-1);
-        eoff.assign(np, (size_t)-1);
-        size_t bits_bytes = 0;
-        if (!dev)
-            for (int p = 0; p < np; ++p) {
-                if (filters && filters[p]) foff[p] = bitmap_slot(bits_bytes, g->segs[p]->n);
-                if (exists && exists[p]) eoff[p] = bitmap_slot(bits_bytes, g->segs[p]->n);
-            }
-        const size_t slot_bytes = (size_t)round_up((int64_t)(sizeof(GroupSlot) * slots.size()), 16);
-        const size_t total = slot_bytes + bits_bytes + (size_t)round_up((int64_t)extra_bytes, 16);
-        if (total == 0) return;
-        auto *pin = (unsigned char *)ws.pg_pin_in.get(total);
-        auto *dbuf = (unsigned char *)ws.pg_slots.get(total);
-        dslots = (const GroupSlot *)dbuf;
-        dbits = dbuf + slot_bytes;
-        dextra = dbuf + slot_bytes + bits_bytes;
-        for (int p = 0; p < np && !dev; ++p) {
-            const size_t bm = (size_t)((g->segs[p]->n + 7) / 8);
-            if (foff[p] != (size_t)-1) std::memcpy(pin + slot_bytes + foff[p], filters[p], bm);
-            if (eoff[p] != (size_t)-1) std::memcpy(pin + slot_bytes + eoff[p], exists[p], bm);
-        }
-        if (extra_bytes) std::memcpy(pin + slot_bytes + bits_bytes, extra, extra_bytes);
-        for (GroupSlot &e : slots) {
-            if (e.part < 0) continue;
-            e.filter = part_filter(e.part);
-            e.exists = part_exists(e.part);
-        }
-        if (!slots.empty()) std::memcpy(pin, slots.data(), sizeof(GroupSlot) * slots.size());
-        MQVS_HIP(hipMemcpyAsync(dbuf, pin, total, hipMemcpyHostToDevice, s));
-    }
-
-    // per-part lists [nparts][nq][k] and the outputs
-    void lists_and_outputs(int32_t *out_part, int64_t *out_ids, float *out_dist) {
-        const size_t nlist = (size_t)nparts() * nq * k, nout = (size_t)nq * k;
-        auto *lbuf = (unsigned char *)ws.pg_lists.get(nlist * 12 + 16);
-        list_ids = (int64_t *)lbuf;
-        list_dist = (float *)(lbuf + nlist * 8);
-        out = ws.io.out(nout, dev, out_ids, out_dist);
-        dpart = dev ? out_part : (int32_t *)ws.pg_part.get(sizeof(int32_t) * nout);
-    }
-    int64_t *part_ids(int p) const { return list_ids + (size_t)p * nq * k; }
-    float *part_dist(int p) const { return list_dist + (size_t)p * nq * k; }
-
-    // the merge (order: the metric whose key orders the lists), and the call's one wait
-    void merge_and_wait(int order, int32_t *out_part, mqvs_part_group_stats &st) {
-        const int np = nparts();
-        const size_t nout = (size_t)nq * k;
-        uint4 *scratch =
-            (int64_t)np * k > kSortCap ? (uint4 *)ws.pg_sort.get(sizeof(uint4) * 2 * (size_t)np * k * nq) : nullptr;
-        launch_merge_shards(np, nq, k, order, list_ids, list_dist, out.ids, out.dist, true, scratch, s, dpart);
-        MQVS_HIP(hipGetLastError());
-        st.launches += 1;
-        ws.io.finish_begin(out, s);
-        int32_t *hpart = nullptr;
-        if (!dev) {
-            hpart = (int32_t *)ws.pg_pin_out.get(sizeof(int32_t) * nout);
-            MQVS_HIP(hipMemcpyAsync(hpart, dpart, sizeof(int32_t) * nout, hipMemcpyDeviceToHost, s));
-        }
-        host_wait(s);
-        ws.io.finish_end(out);
-        if (hpart) std::memcpy(out_part, hpart, sizeof(int32_t) * nout);
-    }
-};
+        },
+        [](GroupSlot &end, const Slice &cur) {
+            end.tile0 = cur.tiles;
+            end.col0 = cur.cols;
+        });
+}
 
 static void group_search(mqvs_part_group *g, const float *queries, int nq, int k, int metric,
                          const uint8_t *const *filters, const uint8_t *const *exists, int32_t *out_part,
@@ -316,8 +204,8 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
     // the slot tables, one copy to the device (GroupCall::stage)
     const float *dq =
         (const float *)ws.io.in(queries, sizeof(float) * (size_t)nq * d, nullptr, nullptr, 0, dev, s).queries;
-    GroupCall c{g, ws, s, dev, nq, k, filters, exists};
-    c.build_slices(fused, [&](int p, GroupSlot &e) {
+    PartGroupCall c{part_rows(g), ws, s, dev, nq, k, filters, exists};
+    build_part_slices(c, g, fused, [&](int p, GroupSlot &e) {
         const mqvs_segment *seg = g->segs[p];
         e.rows = seg->rows;
         e.row_norms = seg->norms;
@@ -393,7 +281,7 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
     }
 
     // ---- the merge, and the call's one wait
-    c.merge_and_wait(metric, out_part, st);
+    c.merge_and_wait(metric, out_part, st.launches);
     if (timing)
         st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     t_group_stats = st;
@@ -445,8 +333,8 @@ static void group_search_binary(mqvs_part_group *g, const uint8_t *queries, int 
     st.looped_parts = nparts - nfused;
 
     // ---- inputs.  The host queries ride with the slot tables and bitmaps
-    GroupCall c{g, ws, s, dev, nq, k, filters, exists};
-    c.build_slices(fused, [&](int p, GroupSlot &e) {
+    PartGroupCall c{part_rows(g), ws, s, dev, nq, k, filters, exists};
+    build_part_slices(c, g, fused, [&](int p, GroupSlot &e) {
         e.codes = g->segs[p]->codes;
         return (e.n + kSmallRows - 1) / kSmallRows;  // plain tiles from row 0 (no chunk arithmetic)
     });
@@ -499,7 +387,7 @@ static void group_search_binary(mqvs_part_group *g, const uint8_t *queries, int 
     }
 
     // ---- the merge, and the call's one wait
-    c.merge_and_wait(kOrder, out_part, st);
+    c.merge_and_wait(kOrder, out_part, st.launches);
     if (timing)
         st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     t_group_stats = st;

@@ -26,6 +26,9 @@ struct Workspace {
     // part-group searches (part_group.hip) keep their own buffers: the
     // per-part searches nested in such a call use the ones above
     GBuf pg_q, pg_qvars, pg_slots, pg_bits, pg_matrix, pg_lists, pg_sort, pg_part;
+    // index-group searches (index_group.hip) share them (pg_matrix: the record regions) and add the
+    // slices' centroid distances and the call's probes + record counters
+    GBuf pg_cdist, pg_probes;
     HostBuf pg_pin_in, pg_pin_out;  // pinned staging: slot table + bitmaps; out_part
     int *host_flags = nullptr;  // pinned (64 ints; the selected-row count record at kCountRec)
     int64_t count_gen = 0;      // generation of the last selected-row count record asked for

@@ -75,7 +75,8 @@ size_t Workspace::free_buffers(bool keep_sticky) {
     size_t b = io.release();
     for (GBuf *x : {&qvars, &qnorms, &qmu, &qlam, &status, &ord, &probe, &tau, &count, &cand, &overflow, &misc, &qhi,
                     &bq, &thr, &cand2, &count2, &gcount, &goff, &glist, &large, &sticky, &surv, &recs, &flags, &p4q,
-                    &qord, &pg_q, &pg_qvars, &pg_slots, &pg_bits, &pg_matrix, &pg_lists, &pg_sort, &pg_part}) {
+                    &qord, &pg_q, &pg_qvars, &pg_slots, &pg_bits, &pg_matrix, &pg_lists, &pg_sort, &pg_part, &pg_cdist,
+                    &pg_probes}) {
         if (keep_sticky && x == &sticky) continue;
         b += x->cap;
         x->release();

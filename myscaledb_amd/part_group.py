@@ -103,6 +103,11 @@ class PartGroup:
         bitmap per part, or None.  Torch CUDA queries: the bitmaps are torch
         CUDA uint8 tensors and the results come back as tensors."""
         m = self.metric if metric is None else metric_id(metric)
+        return self._search(queries, k, m, filters, row_exists, timing)
+
+    def _search(self, queries, k, m, filters, row_exists, timing):
+        """search() with the C call's fifth argument resolved (the metric id;
+        an index group's parameter string)."""
         extra = F_TIMING if timing else 0
         fn = getattr(lib, self._search_fn)
         if _is_torch(queries):
