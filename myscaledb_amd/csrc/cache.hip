@@ -14,7 +14,7 @@
 #include <string>
 #include <unordered_map>
 
-#include "mqvs_internal.h"
+#include "search_host.h"
 
 namespace {
 

@@ -1,15 +1,58 @@
 // group_call.h -- what the group searches (part_group.hip, index_group.hip) do
-// the same way around their grouped kernels: the slot tables of the fused
+// the same way around their grouped kernels: the argument checks and the stats
+// header, the call's device, workspace and stream, the slot tables of the fused
 // parts cut into slices, the call's host inputs staged with them in one copy,
 // the per-part lists, and the merge with the call's one host wait.
 #pragma once
 
+#include <chrono>
 #include <cstring>
 #include <vector>
 
 #include "workspace.h"
 
 namespace mqvs {
+
+// check_search_args, and the list index the merge writes
+inline void check_group_args(const void *group, const char *what, const char *wrong_kind, int nq, int k,
+                             const void *queries, const void *out_part, const void *out_ids, const void *out_dist) {
+    check_search_args(group, what, wrong_kind, nq, k, queries, out_ids, out_dist);
+    if (nq > 0 && k > 0 && !out_part) fail(MQVS_ERR_BAD_ARGUMENTS, "null query or output pointer");
+}
+
+// After a search's own checks: the merge's limit, then the stats header of the
+// call (st, stored as the thread's last) -- all that a call with nq 0 or k 0
+// leaves (false: nothing to search).
+template <typename Stats>
+bool group_begin(int nparts, int nq, int k, Stats &st, Stats &last) {
+    if ((int64_t)nparts * k > ((int64_t)1 << 20)) fail(MQVS_ERR_BAD_ARGUMENTS, "nparts * k above 2^20");
+    st = Stats{};
+    st.parts = nparts;
+    st.nq = nq;
+    st.k = k;
+    last = st;
+    return nq != 0 && k != 0;
+}
+
+// The clock, device, workspace call and stream of one group search
+struct GroupScope {
+    const bool timing;
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    DeviceGuard guard;
+    Workspace &ws;
+    WsCall call;
+    hipStream_t s;
+    GroupScope(int device, uint32_t flags, hipStream_t user_stream)
+        : timing(timing_on(flags)), guard(device), ws(workspace(device)), call(ws),
+          s(user_stream ? user_stream : ws.stream) {
+        ws.last = s;
+    }
+    // host time of the call so far (0 unless timed)
+    double total_ms() const {
+        if (!timing) return 0.0;
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+};
 
 // 16-B aligned offsets of the staged bitmaps in one buffer
 inline size_t bitmap_slot(size_t &total, int64_t n) {

@@ -37,7 +37,6 @@
 // row limit.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <vector>
 
 #include "group_call.h"
@@ -90,8 +89,7 @@ using IndexGroupCall = GroupCall<BivfGroupSlot, IndexSlice>;
 static void igroup_search_binary(mqvs_index_group *g, const uint8_t *queries, int nq, int k, const char *params,
                                  const uint8_t *const *filters, const uint8_t *const *exists, int32_t *out_part,
                                  int64_t *out_ids, float *out_dist, uint32_t flags, hipStream_t user_stream) {
-    check_search_args(g, "index group", nullptr, nq, k, queries, out_ids, out_dist);
-    if (nq > 0 && k > 0 && !out_part) fail(MQVS_ERR_BAD_ARGUMENTS, "null query or output pointer");
+    check_group_args(g, "index group", nullptr, nq, k, queries, out_part, out_ids, out_dist);
     const int nparts = (int)g->idx.size();
 
     // ---- the search parameters: one metric; nprobe per part
@@ -108,22 +106,11 @@ static void igroup_search_binary(mqvs_index_group *g, const uint8_t *queries, in
     for (int p = 0; p < nparts; ++p)
         nprobe[p] =
             explicit_np ? (int)std::min<int64_t>(want_np, g->idx[p]->nlist) : search_nprobe(g->idx[p], pm);
-    if ((int64_t)nparts * k > ((int64_t)1 << 20)) fail(MQVS_ERR_BAD_ARGUMENTS, "nparts * k above 2^20");
-
-    mqvs_index_group_stats st{};
-    st.parts = nparts;
-    st.nq = nq;
-    st.k = k;
-    t_igroup_stats = st;
-    if (nq == 0 || k == 0) return;
-    const bool timing = timing_on(flags);
-    const auto t0 = std::chrono::steady_clock::now();
-
-    DeviceGuard guard(g->device);
-    Workspace &ws = workspace(g->device);
-    WsCall ws_call(ws);
-    hipStream_t s = user_stream ? user_stream : ws.stream;
-    ws.last = s;
+    mqvs_index_group_stats st;
+    if (!group_begin(nparts, nq, k, st, t_igroup_stats)) return;
+    GroupScope sc(g->device, flags, user_stream);
+    Workspace &ws = sc.ws;
+    hipStream_t s = sc.s;
     const bool dev = flags & MQVS_F_DEVICE_PTRS;
     constexpr int kOrder = MQVS_METRIC_L2;  // ascending finite values: ord_asc key, (key, row) ties
     const int cw = g->code_words;
@@ -264,8 +251,7 @@ static void igroup_search_binary(mqvs_index_group *g, const uint8_t *queries, in
     st.items = words[5];
     st.plane_bytes = words[6];
     st.pairs = words[7];
-    if (timing)
-        st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st.total_ms = sc.total_ms();
     t_igroup_stats = st;
 }
 

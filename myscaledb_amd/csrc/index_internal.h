@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "index_kernels.h"
+#include "search_host.h"
 
 struct mqvs_index {
     mqvs_segment *seg = nullptr;   // borrowed: the caller keeps the segment alive

@@ -34,7 +34,7 @@
 // Included by index_internal.h (the host files) and those seven files only.
 #pragma once
 
-#include "mqvs_internal.h"
+#include "flat_kernels.h"
 
 namespace mqvs {
 

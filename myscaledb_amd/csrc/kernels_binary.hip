@@ -28,7 +28,7 @@
 // from flooding the candidate lists.
 #include <cstdlib>
 
-#include "mqvs_internal.h"
+#include "flat_kernels.h"
 
 namespace mqvs {
 

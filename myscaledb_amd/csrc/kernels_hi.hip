@@ -14,7 +14,7 @@
 // a bf16 + fp6-MX split; both streamed more bytes per element for the same
 // survivors and were removed in round 3.)
 //
-// Planes are row-blocked in groups of 16 vectors (mqvs_internal.h,
+// Planes are row-blocked in groups of 16 vectors (flat_kernels.h,
 // kPlaneSlab): vector u, stage s (32 columns) at byte (u >> 4) nst 1024 +
 // plane_step_off(s) + plane_vec_off(u & 15); a stage's 16-vector piece is
 // 1 KiB contiguous (kPlaneSlab 32).
@@ -30,7 +30,7 @@
 #include <atomic>
 #include <cstdlib>
 
-#include "mqvs_internal.h"
+#include "flat_kernels.h"
 #include "scan_emit.h"
 #include "tuning.h"
 

@@ -23,7 +23,7 @@
 //   k_sizes_scan_*  array sizes (UInt64 per row) -> element offsets.
 //   k_array_rows    the copy loop of :1381-1393: FLT_MAX fill, first
 //                   min(size, d) elements of a non-empty array, nonempty flag.
-#include "mqvs_internal.h"
+#include "flat_kernels.h"
 
 namespace mqvs {
 

@@ -71,7 +71,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "mqvs_internal.h"
+#include "flat_kernels.h"
 #include "scan_emit.h"
 #include "tuning.h"
 

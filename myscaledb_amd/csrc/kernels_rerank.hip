@@ -8,7 +8,7 @@
 // an fma-chain inner product; cosine with the chunk's query variant), then
 // sort (key, chunk, ip, row) in LDS exactly like the search's final select.
 // With every row of the segment as candidates the result equals mqvs_search.
-#include "mqvs_internal.h"
+#include "flat_kernels.h"
 #include "select_common.h"
 
 namespace mqvs {
@@ -109,7 +109,7 @@ __device__ inline void rerank_emit(uint4 *recs, uint4 *g, int ncand, int k, int 
     }
 }
 
-// Bound pruning (index re-rank; RerankPrune in mqvs_internal.h): how many of
+// Bound pruning (index re-rank; RerankPrune in flat_kernels.h): how many of
 // query q's candidates -- sorted by their approximate value a -- can reach the
 // exact top k.  With B the bound on |a - exact| (k_query_bound for query
 // variant 0, plus |x_v - x_0| |y|max for the cosine variant x_v the exact

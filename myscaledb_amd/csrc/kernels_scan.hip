@@ -23,8 +23,8 @@
 //    APPEND -- append only (raw, row) with key <= threshold to a per-query
 //              candidate list (a few thousand entries).
 // Validity (PREWHERE bitmap, lightweight-delete mask, empty arrays, metric
-// quirks) is applied in the epilogue; see mqvs_internal.h key32().
-#include "mqvs_internal.h"
+// quirks) is applied in the epilogue; see flat_kernels.h key32().
+#include "flat_kernels.h"
 
 namespace mqvs {
 

@@ -4,7 +4,7 @@
 // merge of MergeTreeVSManager::searchWrapper (MergeTreeVSManager.cpp:1653-1679)
 // and the cross-part multimap merge (MergeTreeBaseSearchManager.cpp:207-297).
 // The reference's cumulative result is the k best rows under one total order
-// (mqvs_internal.h key32 + tie rules); here it is found in three steps:
+// (flat_kernels.h key32 + tie rules); here it is found in three steps:
 //   k_probe_select  radix select (4 x 8-bit digits) of the k-th key over the
 //                   dense probe values -> per-query threshold tau, and the
 //                   probe rows with key <= tau become the first candidates;

@@ -26,7 +26,6 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
-#include <chrono>
 #include <vector>
 
 #include "group_call.h"
@@ -134,14 +133,37 @@ static void build_part_slices(PartGroupCall &c, const mqvs_part_group *g, const 
         });
 }
 
+// The fused slices of a call: the dense matrix sized to the widest slice; per
+// slice the grouped scan (scan(p, slots, slice), skipped when the slice has
+// no tiles), then the grouped select by `order`'s key into the per-part
+// lists.  p: the scan's base parameters but for the matrix.
+template <typename Scan>
+static void scan_and_select(PartGroupCall &c, ScanParams &p, int order, int *fl, int32_t &launches, Scan &&scan) {
+    int64_t ld = 0;
+    for (const Slice &sl : c.slices) ld = std::max(ld, sl.cols);
+    float *matrix = (float *)c.ws.pg_matrix.get(sizeof(float) * (size_t)c.nq * std::max<int64_t>(ld, 1));
+    p.probe = matrix;
+    for (const Slice &sl : c.slices) {
+        const GroupSlot *slots = c.dslots + sl.first_slot;
+        p.probe_ld = sl.cols;
+        if (sl.tiles > 0) {
+            scan(p, slots, sl);
+            MQVS_HIP(hipGetLastError());
+            launches += 1;
+        }
+        launch_select_group(matrix, sl.cols, slots, sl.nslots, c.nq, c.k, order, c.list_ids, c.list_dist, fl, c.s);
+        MQVS_HIP(hipGetLastError());
+        launches += 1;
+    }
+}
+
 static void group_search(mqvs_part_group *g, const float *queries, int nq, int k, int metric,
                          const uint8_t *const *filters, const uint8_t *const *exists, int32_t *out_part,
                          int64_t *out_ids, float *out_dist, uint32_t flags, hipStream_t user_stream) {
-    check_search_args(g, "part group",
-                      g && g->binary ? "binary (FixedString) part group: search it with mqvs_part_group_search_binary"
-                                     : nullptr,
-                      nq, k, queries, out_ids, out_dist);
-    if (nq > 0 && k > 0 && !out_part) fail(MQVS_ERR_BAD_ARGUMENTS, "null query or output pointer");
+    check_group_args(g, "part group",
+                     g && g->binary ? "binary (FixedString) part group: search it with mqvs_part_group_search_binary"
+                                    : nullptr,
+                     nq, k, queries, out_part, out_ids, out_dist);
     const bool cos = metric == MQVS_METRIC_COSINE;
     if (metric != MQVS_METRIC_L2 && metric != MQVS_METRIC_IP && !cos)
         fail(MQVS_ERR_NOT_IMPLEMENTED, "Metric not implemented in brute force search for Float32 Vector");
@@ -149,21 +171,11 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
         fail(MQVS_ERR_LOGICAL, "part group was prepared for a different metric (cosine segments are "
                                "normalised in HBM and serve only cosine searches)");
     const int nparts = (int)g->segs.size();
-    if ((int64_t)nparts * k > ((int64_t)1 << 20)) fail(MQVS_ERR_BAD_ARGUMENTS, "nparts * k above 2^20");
-    mqvs_part_group_stats st{};
-    st.parts = nparts;
-    st.nq = nq;
-    st.k = k;
-    t_group_stats = st;
-    if (nq == 0 || k == 0) return;
-    const bool timing = timing_on(flags);
-    const auto t0 = std::chrono::steady_clock::now();
-
-    DeviceGuard guard(g->device);
-    Workspace &ws = workspace(g->device);
-    WsCall ws_call(ws);
-    hipStream_t s = user_stream ? user_stream : ws.stream;
-    ws.last = s;
+    mqvs_part_group_stats st;
+    if (!group_begin(nparts, nq, k, st, t_group_stats)) return;
+    GroupScope sc(g->device, flags, user_stream);
+    Workspace &ws = sc.ws;
+    hipStream_t s = sc.s;
     const bool dev = flags & MQVS_F_DEVICE_PTRS;
     const int d = g->d;
     const int64_t qstride = round_up(d, 32);
@@ -223,10 +235,6 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
     });
     c.stage(nullptr, 0);
     c.lists_and_outputs(out_part, out_ids, out_dist);
-    const std::vector<Slice> &slices = c.slices;
-    const GroupSlot *dslots = c.dslots;
-    int64_t *list_ids = c.list_ids;
-    float *list_dist = c.list_dist;
 
     // ---- the fused route
     if (nfused > 0) {
@@ -242,9 +250,6 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
                           maxv, qnorms, qmu, qlam, fl + 4, s);
         MQVS_HIP(hipGetLastError());
         st.launches += 2;
-        int64_t ld = 0;
-        for (const Slice &sl : slices) ld = std::max(ld, sl.cols);
-        float *matrix = (float *)ws.pg_matrix.get(sizeof(float) * (size_t)nq * std::max<int64_t>(ld, 1));
         ScanParams p{};
         p.d = d;
         p.nq = nq;
@@ -255,22 +260,12 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
         p.maxv = maxv;
         p.blas_nq = nq;
         p.num_qblocks = (nq + kMfmaQ - 1) / kMfmaQ;
-        p.probe = matrix;
-        for (const Slice &sl : slices) {
-            p.probe_ld = sl.cols;
-            if (sl.tiles > 0) {
-                if (batch)
-                    launch_scan_group_mfma(p, dslots + sl.first_slot, sl.nslots, sl.tiles, metric, s);
-                else
-                    launch_scan_group(p, dslots + sl.first_slot, sl.nslots, sl.tiles, metric, s);
-                MQVS_HIP(hipGetLastError());
-                st.launches += 1;
-            }
-            launch_select_group(matrix, sl.cols, dslots + sl.first_slot, sl.nslots, nq, k, metric, list_ids, list_dist,
-                                fl, s);
-            MQVS_HIP(hipGetLastError());
-            st.launches += 1;
-        }
+        scan_and_select(c, p, metric, fl, st.launches, [&](const ScanParams &sp, const GroupSlot *slots, const Slice &sl) {
+            if (batch)
+                launch_scan_group_mfma(sp, slots, sl.nslots, sl.tiles, metric, s);
+            else
+                launch_scan_group(sp, slots, sl.nslots, sl.tiles, metric, s);
+        });
     }
 
     // ---- the per-part route (each search ends in its own host wait)
@@ -282,8 +277,7 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
 
     // ---- the merge, and the call's one wait
     c.merge_and_wait(metric, out_part, st.launches);
-    if (timing)
-        st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st.total_ms = sc.total_ms();
     t_group_stats = st;
 }
 
@@ -295,28 +289,17 @@ static void group_search(mqvs_part_group *g, const float *queries, int nq, int k
 static void group_search_binary(mqvs_part_group *g, const uint8_t *queries, int nq, int k, int metric,
                                 const uint8_t *const *filters, const uint8_t *const *exists, int32_t *out_part,
                                 int64_t *out_ids, float *out_dist, uint32_t flags, hipStream_t user_stream) {
-    check_search_args(g, "part group",
-                      g && !g->binary ? "Float32 part group: search it with mqvs_part_group_search" : nullptr, nq, k,
-                      queries, out_ids, out_dist);
-    if (nq > 0 && k > 0 && !out_part) fail(MQVS_ERR_BAD_ARGUMENTS, "null query or output pointer");
+    check_group_args(g, "part group",
+                     g && !g->binary ? "Float32 part group: search it with mqvs_part_group_search" : nullptr, nq, k,
+                     queries, out_part, out_ids, out_dist);
     if (metric != MQVS_METRIC_HAMMING && metric != MQVS_METRIC_JACCARD)
         fail(MQVS_ERR_NOT_IMPLEMENTED, "Metric not implemented in brute force search for Binary Vector");
     const int nparts = (int)g->segs.size();
-    if ((int64_t)nparts * k > ((int64_t)1 << 20)) fail(MQVS_ERR_BAD_ARGUMENTS, "nparts * k above 2^20");
-    mqvs_part_group_stats st{};
-    st.parts = nparts;
-    st.nq = nq;
-    st.k = k;
-    t_group_stats = st;
-    if (nq == 0 || k == 0) return;
-    const bool timing = timing_on(flags);
-    const auto t0 = std::chrono::steady_clock::now();
-
-    DeviceGuard guard(g->device);
-    Workspace &ws = workspace(g->device);
-    WsCall ws_call(ws);
-    hipStream_t s = user_stream ? user_stream : ws.stream;
-    ws.last = s;
+    mqvs_part_group_stats st;
+    if (!group_begin(nparts, nq, k, st, t_group_stats)) return;
+    GroupScope sc(g->device, flags, user_stream);
+    Workspace &ws = sc.ws;
+    hipStream_t s = sc.s;
     const bool dev = flags & MQVS_F_DEVICE_PTRS;
     constexpr int kOrder = MQVS_METRIC_L2;  // ascending finite values: ord_asc key, (key, row) ties
 
@@ -341,10 +324,6 @@ static void group_search_binary(mqvs_part_group *g, const uint8_t *queries, int 
     c.stage(dev ? nullptr : queries, dev ? 0 : (size_t)nq * g->code_bytes);
     const uint8_t *dq = dev ? queries : c.dextra;  // [nq][code_bytes] on the device
     c.lists_and_outputs(out_part, out_ids, out_dist);
-    const std::vector<Slice> &slices = c.slices;
-    const GroupSlot *dslots = c.dslots;
-    int64_t *list_ids = c.list_ids;
-    float *list_dist = c.list_dist;
 
     // ---- the fused route
     if (nfused > 0) {
@@ -355,28 +334,15 @@ static void group_search_binary(mqvs_part_group *g, const uint8_t *queries, int 
         // the query codes, zero padded to the segments' row stride, once per call
         uint32_t *qc = (uint32_t *)ws.pg_qvars.get((size_t)nq * g->code_words * 4);
         upload_codes(qc, g->code_words, dq, g->code_bytes, nq, true, s);
-        int64_t ld = 0;
-        for (const Slice &sl : slices) ld = std::max(ld, sl.cols);
-        float *matrix = (float *)ws.pg_matrix.get(sizeof(float) * (size_t)nq * std::max<int64_t>(ld, 1));
         ScanParams p{};
         p.d = g->d;
         p.nq = nq;
         p.qcodes = qc;
         p.code_words = g->code_words;
         p.nbits = g->d;
-        p.probe = matrix;
-        for (const Slice &sl : slices) {
-            p.probe_ld = sl.cols;
-            if (sl.tiles > 0) {
-                launch_scan_group_binary(p, dslots + sl.first_slot, sl.nslots, sl.tiles, metric, s);
-                MQVS_HIP(hipGetLastError());
-                st.launches += 1;
-            }
-            launch_select_group(matrix, sl.cols, dslots + sl.first_slot, sl.nslots, nq, k, kOrder, list_ids, list_dist,
-                                fl, s);
-            MQVS_HIP(hipGetLastError());
-            st.launches += 1;
-        }
+        scan_and_select(c, p, kOrder, fl, st.launches, [&](const ScanParams &sp, const GroupSlot *slots, const Slice &sl) {
+            launch_scan_group_binary(sp, slots, sl.nslots, sl.tiles, metric, s);
+        });
     }
 
     // ---- the per-part route (each search ends in its own host wait)
@@ -388,8 +354,7 @@ static void group_search_binary(mqvs_part_group *g, const uint8_t *queries, int 
 
     // ---- the merge, and the call's one wait
     c.merge_and_wait(kOrder, out_part, st.launches);
-    if (timing)
-        st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st.total_ms = sc.total_ms();
     t_group_stats = st;
 }
 

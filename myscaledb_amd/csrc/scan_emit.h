@@ -2,7 +2,7 @@
 // stores dense approximate values, APPEND keeps rows over the threshold.
 #pragma once
 
-#include "mqvs_internal.h"
+#include "flat_kernels.h"
 
 namespace mqvs {
 

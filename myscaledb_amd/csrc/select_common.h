@@ -1,7 +1,7 @@
 // select_common.h -- block-wide radix select, float-row visitor and LDS bitonic
 // sort shared by the selection kernels (kernels_select.hip, kernels_bf16.hip).
 #pragma once
-#include "mqvs_internal.h"
+#include "flat_kernels.h"
 
 namespace mqvs {
 

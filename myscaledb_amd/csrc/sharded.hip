@@ -57,7 +57,6 @@
 #include <vector>
 
 #include "index_internal.h"
-#include "mqvs_internal.h"
 
 namespace mqvs {
 

@@ -4,7 +4,8 @@
 
 #include <mutex>
 
-#include "mqvs_internal.h"
+#include "flat_kernels.h"
+#include "search_host.h"
 
 namespace mqvs {
 

@@ -53,7 +53,7 @@ def chunk_ordinal_base(r0: int, granule: int, n: int, nonempty=None, filter_bits
     re-normalises a cosine query for): a chunk is searched iff it holds a
     non-empty row that, under a PREWHERE filter, also passes it and is not
     deleted (MergeTreeVSManager.cpp:960-1536; the device twin is
-    kernels_misc.hip k_chunk_active)."""
+    kernels_filter.hip k_chunk_active)."""
     nch = r0 // granule
     if nch == 0:
         return 0

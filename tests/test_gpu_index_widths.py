@@ -220,7 +220,7 @@ def test_index_wide_pruned_rerank_equals_full(mq, qmode, nq):
 
 
 def _bf16(x):
-    """f32_to_bf16_rn (mqvs_internal.h): round to nearest even, as float64."""
+    """f32_to_bf16_rn (flat_kernels.h): round to nearest even, as float64."""
     u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
     u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
     return u.astype(np.uint32).view(np.float32).astype(np.float64)

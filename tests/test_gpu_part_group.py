@@ -385,3 +385,83 @@ def test_scratch_budget_slices(mq):
     assert_same(got, whole, "slices")
     assert np.array_equal(got[1], loop[0]) and np.array_equal(got[2].view(np.uint32), loop[1].view(np.uint32))
     assert st["fused_parts"] == 4 and st["launches"] > st_whole["launches"]
+
+
+# ---------------------------------------------------------------- the call's frame: refusals and stats
+def test_refusals_in_call_order(mq):
+    """Status and mqvs_last_error text of every refusal a search raises before
+    it looks at the parts, and which one is reported when two apply: the
+    checks run in the order of this list."""
+    from myscaledb_amd import _lib
+    lib = _lib.lib
+    seg = mq.VectorScanSegment.from_rows(O.generate(1080, 1, 0, 300, 8), metric="L2", granule=256)
+    seg_b = mq.BinaryVectorScanSegment.from_codes(np.zeros((64, 8), np.uint8))
+    g, bg, big = mq.PartGroup([seg] * 3), mq.BinaryPartGroup([seg_b]), mq.PartGroup([seg] * 65)
+    queries = O.generate(1090, 1, 0, 1, 8)
+    part, ids, dist = np.full(16385, 77, np.int32), np.full(16385, 77, np.int64), np.full(16385, 77, np.float32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+
+    def refusal(group, nq=1, k=3, metric=_lib.METRIC_L2, out_part=True):
+        rc = lib.mqvs_part_group_search(group._h if group else None, p(queries), nq, k, metric, None, None,
+                                        p(part) if out_part else None, p(ids), p(dist), 0, None)
+        return rc, lib.mqvs_last_error().decode()
+
+    bad = _lib.ERR_BAD_ARGUMENTS
+    null_group = (bad, "null part group")
+    kind = (_lib.ERR_LOGICAL, "binary (FixedString) part group: search it with mqvs_part_group_search_binary")
+    negative = (bad, "nq and k must be non-negative")
+    null_ptr = (bad, "null query or output pointer")
+    k_max = (bad, "k above 16384 not supported")
+    no_metric = (_lib.ERR_NOT_IMPLEMENTED, "Metric not implemented in brute force search for Float32 Vector")
+    too_many = (bad, "nparts * k above 2^20")
+    try:
+        assert refusal(None) == null_group
+        assert refusal(bg) == kind
+        assert refusal(g, nq=-1) == negative and refusal(g, k=-1) == negative
+        assert refusal(g, out_part=False) == null_ptr
+        assert refusal(g, k=16385) == k_max
+        assert refusal(g, metric=_lib.METRIC_HAMMING) == no_metric
+        assert refusal(big, k=16384) == too_many
+        # two at once
+        assert refusal(None, nq=-1, out_part=False) == null_group
+        assert refusal(bg, nq=-1) == kind and refusal(bg, out_part=False) == kind
+        assert refusal(bg, metric=_lib.METRIC_HAMMING) == kind
+        assert refusal(g, nq=-1, metric=_lib.METRIC_HAMMING) == negative
+        assert refusal(g, k=16385, out_part=False) == k_max
+        assert refusal(g, metric=_lib.METRIC_HAMMING, out_part=False) == null_ptr
+        assert refusal(big, k=16385) == k_max
+        assert refusal(big, k=16384, out_part=False) == null_ptr
+        assert refusal(big, k=16384, metric=_lib.METRIC_HAMMING) == no_metric
+        assert np.all(part == 77) and np.all(ids == 77) and np.all(dist == 77)
+    finally:
+        for x in (g, bg, big, seg, seg_b):
+            x.free()
+
+
+def test_stats_of_a_mixed_group(mq):
+    """Every field of mqvs_part_group_last_stats at nq 1: parts of 5 and 300
+    rows fused, the part of 700 rows over a row limit of 512 on the per-part
+    route.  launches: the status fill and the query prep, one scan and one
+    select (one slice), the merge.  A call with nq 0 or k 0 leaves the header."""
+    from myscaledb_amd import _lib
+    parts = [O.generate(1180 + p, 1, 0, n, 8) for p, n in enumerate((5, 300, 700))]
+    queries = O.generate(1190, 1, 0, 1, 8)
+    want, _ = oracle_group(parts, queries, 3, "L2", 256)
+    segs, group = make_group(mq, parts, "L2", 256)
+    prev = mq.set_part_group_rows(512)
+    try:
+        got = group.search(queries, 3)
+        st = group.last_stats()
+        empty = []
+        for nq, k in ((0, 3), (1, 0)):
+            _lib.check(_lib.lib.mqvs_part_group_search(group._h, None, nq, k, _lib.METRIC_L2, None, None, None, None,
+                                                       None, 0, None))
+            empty.append(group.last_stats())
+    finally:
+        mq.set_part_group_rows(prev)
+        free_all(group, segs)
+    assert_same(got, want, "mixed group")
+    assert st == dict(total_ms=0.0, fused_rows=305, parts=3, fused_parts=2, looped_parts=1, launches=5, redo=0,
+                      nq=1, k=3, batch=0)
+    header = dict(total_ms=0.0, fused_rows=0, parts=3, fused_parts=0, looped_parts=0, launches=0, redo=0, batch=0)
+    assert empty == [dict(header, nq=0, k=3), dict(header, nq=1, k=0)]

@@ -362,3 +362,30 @@ def test_cosine_long_variant_chain(mq):
         free_all(group, segs)
     assert_same(got, want, "cosine, 65 chunk ordinals")
     assert st["fused_parts"] == 3 and st["batch"] == 1
+
+
+# ---------------------------------------------------------------- the call's frame: stats
+def test_stats_of_a_mixed_group(mq):
+    """Every field of mqvs_part_group_last_stats at nq 20 with the batch route
+    on up to 512 rows: parts of 5 and 300 rows fused, the part of 700 rows on
+    the per-part route.  launches: the status fill and the query prep, one
+    scan and one select (one slice), the merge.  With the route off every part
+    is looped and only the merge is counted."""
+    parts = [O.generate(1180 + p, 1, 0, n, 8) for p, n in enumerate((5, 300, 700))]
+    queries = O.generate(1190, 1, 0, 20, 8)
+    want, _ = oracle_group(parts, queries, 3, "L2", 256)
+    segs, group = make_group(mq, parts, "L2", 256)
+    try:
+        with batch_route(mq, 512):
+            got = group.search(queries, 3)
+            st = group.last_stats()
+        off = group.search(queries, 3)
+        st_off = group.last_stats()
+    finally:
+        free_all(group, segs)
+    assert_same(got, want, "mixed group")
+    assert_same(off, want, "route off")
+    assert st == dict(total_ms=0.0, fused_rows=305, parts=3, fused_parts=2, looped_parts=1, launches=5, redo=0,
+                      nq=20, k=3, batch=1)
+    assert st_off == dict(total_ms=0.0, fused_rows=0, parts=3, fused_parts=0, looped_parts=3, launches=1, redo=0,
+                          nq=20, k=3, batch=0)

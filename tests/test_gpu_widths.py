@@ -30,7 +30,7 @@ planes, launch_exact_rerank on the default path): float4 rows when
 d % 4 == 0, scalar loads otherwise; the one-wave re-rank only when
 d % 4 == 0 and nq <= 16.  The re-rank's formula follows faiss: direct below
 nq 20, BLAS from 20.
-launch_query_prep (kernels_misc.hip:501-532): the register kernel
+launch_query_prep (kernels_qprep.hip): the register kernel
   k_query_prep<J> with J = 2, 4, 8, 12, 16, 24 for d <= 128, 256, 512, 768,
   1024, 1536; k_query_prep_lds above 1536.
 

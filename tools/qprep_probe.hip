@@ -1,9 +1,9 @@
-// Timing of the cosine query prep (k_query_prep, kernels_misc.hip) on the
+// Timing of the cosine query prep (k_query_prep, kernels_qprep.hip) on the
 // bench's query distributions: nq queries of generator mode m (held-out rows
 // n .. n + nq, as tools/index_sweep.py draws them), maxv 12; prints the kernel
 // time and the histogram of mu + lambda (normalisations to the first repeat).
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off tools/qprep_probe.hip -o tools/bin/qprep_probe
-#include "../myscaledb_amd/csrc/kernels_misc.hip"
+#include "../myscaledb_amd/csrc/kernels_qprep.hip"
 
 #include <cstdio>
 #include <map>

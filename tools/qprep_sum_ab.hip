@@ -1,11 +1,11 @@
-// A/B of the cosine query prep's sequential square sum (kernels_misc.hip
+// A/B of the cosine query prep's sequential square sum (kernels_qprep.hip
 // k_query_prep): SUMV 0 = v_readlane walk, 1 = LDS broadcast walk, 2 = the
 // LDS walk software-pipelined, 3 = register phases (seq_sq_sum_lanes).  All must write bit-identical variant tables;
 // prints the best of 20 launches at nq = 1 and nq = 1000 (generator mode 1,
 // d = 768, maxv 32), and the floor of a 768-long dependent add chain from
 // registers (chain_us: one wave, `reps` chains, no loads) for scale.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off tools/qprep_sum_ab.hip -o tools/bin/qprep_sum_ab
-#include "../myscaledb_amd/csrc/kernels_misc.hip"
+#include "../myscaledb_amd/csrc/kernels_qprep.hip"
 
 #include <cstdio>
 #include <cstring>
@@ -55,7 +55,7 @@ static float run(const float *q, int nq, int d, int maxv, float *qv, float *qn, 
         (void)hipMemset(st, 0, 16);
         (void)hipEventRecord(a);
         hipLaunchKernelGGL((k_query_prep<12, V, LS>), dim3(nq), dim3(64), sig, 0, q, nq, d, MQVS_METRIC_COSINE, 0, qv, maxv,
-                           qn, mu, lam, st, 0);
+                           qn, mu, lam, st, 0, nullptr);
         (void)hipEventRecord(b);
         (void)hipEventSynchronize(b);
         float ms;

@@ -1,5 +1,5 @@
 // Microbenchmark of the sequential fp32 sum of squares (k_query_prep's chain,
-// kernels_misc.hip): readlane walk vs LDS float4 walk, 1000 waves x R
+// kernels_qprep.hip): readlane walk vs LDS float4 walk, 1000 waves x R
 // normalisations of a 768-vector.  Checks both give the same bits.
 //   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off tools/seqsum_probe.hip -o /tmp/seqsum && /tmp/seqsum
 #include <hip/hip_runtime.h>
