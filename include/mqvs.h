@@ -517,7 +517,19 @@ int mqvs_segment_create_from_column(const uint8_t *data_bin, int64_t data_bytes,
  * (reinterpret as int32_t*, padding -1 / INT32_MAX, faiss::hammings_knn_mc);
  * Jaccard writes floats (padding -1 / FLT_MAX).  Float metrics ->
  * MQVS_ERR_NOT_IMPLEMENTED ("Metric not implemented in brute force search
- * for Binary Vector"), as BruteForceSearch.h:107. */
+ * for Binary Vector"), as BruteForceSearch.h:107.
+ *
+ * mqvs_set_binary_batch (process-wide, off by default): min_nq >= 1 sends
+ * every binary brute-force search of nq >= min_nq -- mqvs_search_binary,
+ * mqvs_knn_binary_raw, the per-part legs of binary part groups -- through the
+ * i8 MFMA scan instead of the popcount scan: the code bits as 0/1 bytes on
+ * v_mfma_i32_16x16x64_i8 give popcount(x & q) exactly, and both distances are
+ * integer expressions of it, so ids and distance bits do not change.  0 turns
+ * the route off; a negative value is MQVS_ERR_BAD_ARGUMENTS and leaves the
+ * setting unchanged.  Read once per call.  mqvs_binary_batch reads the setting
+ * (min_nq may be NULL). */
+int mqvs_set_binary_batch(int32_t min_nq);
+int mqvs_binary_batch(int32_t *min_nq);
 int mqvs_segment_create_binary(const uint8_t *codes, int64_t n, int32_t dim_bits, int32_t metric,
                                int64_t granule_rows, int64_t row_offset, uint32_t flags,
                                mqvs_segment_t *out);
@@ -766,7 +778,12 @@ int mqvs_index_probes(mqvs_index_t idx, const float *queries, int32_t nq, const 
  * for bit.
  * Build params: metric_type (Hamming | Jaccard, default the segment's; other
  * metrics MQVS_ERR_NOT_IMPLEMENTED), alpha, nlist, kmeans_iters, sample --
- * defaults and ranges as above.  The list count is never chosen from the data.
+ * defaults and ranges as above -- and
+ *   assign       valu | mfma (default valu): the kernel of the assignment
+ *                passes below, row-per-lane popcounts or the i8 MFMA; the
+ *                index is the same bit for bit; any other value fails with
+ *                MQVS_ERR_BAD_ARGUMENTS (the float build refuses the key)
+ * The list count is never chosen from the data.
  * Parts of 2^31 or more rows are MQVS_ERR_NOT_IMPLEMENTED.  The build is
  * integer arithmetic only, hence deterministic.  The coarse metric is Hamming
  * for both metrics (Jaccard parts are partitioned by Hamming, scanned with
@@ -999,7 +1016,9 @@ typedef struct {
     int32_t nq;
     int32_t k;
     int32_t path;           /* 0 = VALU direct formula (nq < 20), 1 = fp32 MFMA,
-                               2 = bf16 MFMA pre-filter + exact fp32 re-rank */
+                               2 = bf16 MFMA pre-filter + exact fp32 re-rank,
+                               3 = binary popcount scan, 4 = binary i8 MFMA
+                               scan (mqvs_set_binary_batch) */
     int32_t rescans;        /* candidate-overflow re-scans / fallbacks */
     int32_t segments;       /* main-scan segments (threshold refinements + 1) */
     int32_t gather;         /* 1: selective PREWHERE, the scan walked the gather list

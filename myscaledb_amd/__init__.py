@@ -9,9 +9,11 @@ from . import _lib  # noqa: F401  (loads libmqvs.so, raises if absent)
 from .vector_scan import (  # noqa: F401
     BinaryVectorScanSegment,
     VectorScanSegment,
+    binary_batch,
     init,
     merge_shards,
     pack_bitmap,
+    set_binary_batch,
     try_brute_force_search,
     try_brute_force_search_binary,
     vector_scan_without_index,
@@ -21,5 +23,5 @@ from .part_group import (BinaryPartGroup, PartGroup, part_group_batch, set_part_
                          set_part_group_binary_rows, set_part_group_rows)
 from .index_group import BinaryIndexGroup  # noqa: F401
 
-__all__ = ["PartGroup", "BinaryPartGroup", "BinaryIndexGroup", "set_part_group_binary_rows", "set_part_group_rows", "set_part_group_batch", "part_group_batch", "index_blob_info","BinaryVectorScanSegment", "try_brute_force_search_binary", "VectorScanSegment", "init", "merge_shards", "pack_bitmap",
+__all__ = ["PartGroup", "BinaryPartGroup", "BinaryIndexGroup", "set_part_group_binary_rows", "set_part_group_rows", "set_part_group_batch", "part_group_batch", "set_binary_batch", "binary_batch", "index_blob_info","BinaryVectorScanSegment", "try_brute_force_search_binary", "VectorScanSegment", "init", "merge_shards", "pack_bitmap",
            "try_brute_force_search", "vector_scan_without_index", "VectorIndex", "BinaryVectorIndex"]

@@ -63,6 +63,7 @@ SYMBOLS = [
     "mqvs_cache_remove", "mqvs_cache_stats", "mqvs_inject_fault", "mqvs_set_wait_mode",
     "mqvs_part_group_create", "mqvs_part_group_free", "mqvs_part_group_info", "mqvs_part_group_search",
     "mqvs_part_group_last_stats", "mqvs_set_part_group_rows", "mqvs_set_part_group_batch", "mqvs_part_group_batch",
+    "mqvs_set_binary_batch", "mqvs_binary_batch",
     "mqvs_part_group_search_binary", "mqvs_set_part_group_binary_rows",
     "mqvs_index_group_create", "mqvs_index_group_free", "mqvs_index_group_info", "mqvs_index_group_search_binary",
     "mqvs_index_group_last_stats",
@@ -236,6 +237,8 @@ def _load(path=LIB_PATH):
         "mqvs_set_part_group_rows": ([I64], I64),
         "mqvs_set_part_group_batch": ([I64, I32], ctypes.c_int),
         "mqvs_part_group_batch": ([P, P], ctypes.c_int),
+        "mqvs_set_binary_batch": ([I32], ctypes.c_int),
+        "mqvs_binary_batch": ([P], ctypes.c_int),
         "mqvs_part_group_search_binary": ([P, P, I32, I32, I32, P, P, P, P, P, U32, P], ctypes.c_int),
         "mqvs_set_part_group_binary_rows": ([I64], I64),
         "mqvs_index_group_create": ([P, I32, P], ctypes.c_int),

@@ -19,6 +19,7 @@
 //   kernels_p4.hip       k_scan_p4* (the batch scan at one wave per SIMD), k_ord_planes
 //   kernels_rerank.hip   k_exact_rerank, k_rerank_ids
 //   kernels_binary.hip   k_scan_binary*, k_scan_group_binary, k_hamming_to_int
+//   kernels_binary_mfma.hip  k_bin_expand, k_scan_binary_mfma, k_bivf_assign_mfma (the i8 MFMA route)
 //   kernels_qprep.hip    k_query_prep, k_query_prep_lds
 //   kernels_filter.hip   the PREWHERE gather list, chunk ordinals, the decoupled-part filter
 //   kernels_segprep.hip  k_row_norms, k_normalize_rows, k_generate, k_pack
@@ -219,6 +220,23 @@ __device__ inline bool row_valid(const ScanParams &p, int64_t r) {
     return true;
 }
 
+// the dense PROBE value of a binary row (every binary scan: kernels_binary.hip,
+// kernels_binary_mfma.hip): its distance from a = popcount(q ^ y) (Hamming) or
+// a = popcount(q & y), b = popcount(q | y) (Jaccard); NaN when the row is not
+// valid (or, Hamming, at distance nbits)
+template <int METRIC>
+__device__ __forceinline__ float bin_probe_value(uint32_t a, uint32_t b, bool valid_row, int nbits) {
+    float raw;
+    bool valid = valid_row;
+    if (METRIC == MQVS_METRIC_HAMMING) {
+        raw = (float)a;
+        valid = valid && (int)a < nbits;
+    } else {
+        raw = a == 0u ? 1.0f : (float)(b - a) / (float)b;
+    }
+    return valid ? raw : __builtin_nanf("");
+}
+
 // ---------------------------------------------------------------------------
 // Part groups (part_group.hip): one slot per part of a grouped launch.  The
 // grouped scan maps workgroup tiles [tile0, next slot's tile0) to the part and
@@ -387,6 +405,27 @@ void launch_scan_binary(const ScanParams &p, int metric, bool probe, hipStream_t
 void launch_scan_group_binary(const ScanParams &base, const GroupSlot *slots, int nslots, int64_t tiles, int metric,
                               hipStream_t s);
 void launch_hamming_to_int(const int64_t *ids, float *dist, int64_t m, hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// kernels_binary_mfma.hip (binary vectors on the i8 MFMA)
+// bytes of the expanded plane of ncols codes (columns padded to 16)
+inline size_t bin_plane_bytes(int64_t ncols, int code_words) {
+    return (size_t)((ncols + 15) / 16 * 16) * (size_t)code_words * 32;
+}
+// plane[col][k] = bit k of codes[col] as a 0/1 byte, pop[col] = popcount of the
+// code; both cover ncols rounded up to 16 columns (padding: zeros)
+void launch_bin_expand(const uint32_t *codes, int ncols, int code_words, uint8_t *plane, uint32_t *pop,
+                       hipStream_t s);
+// the columns of a product in operand form (launch_bin_expand's outputs)
+struct BinPlane {
+    const uint8_t *plane;   // [columns rounded up to 16][code_words * 32] codes as 0/1 bytes
+    const uint32_t *pop;    // [columns rounded up to 16] popcount of each code
+};
+// launch_scan_binary's contract on the i8 MFMA (any nq; q: p.qcodes through
+// launch_bin_expand; p.tiles / p.tile_rows are not read).  The plane travels
+// beside ScanParams, not in it: the block's layout is every other scan
+// kernel's argument layout.
+void launch_scan_binary_mfma(const ScanParams &p, const BinPlane &q, int metric, bool probe, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // kernels_qprep.hip

@@ -545,7 +545,15 @@ int binary_metric_of(const std::string &name, const char *what) {
 
 static mqvs_index *build_binary_impl(mqvs_segment *seg, const char *params) {
     const auto pm = parse_params(params);
-    check_keys(pm, {"alpha", "metric_type", "nlist", "kmeans_iters", "sample"}, "index");
+    check_keys(pm, {"alpha", "metric_type", "nlist", "kmeans_iters", "sample", "assign"}, "index");
+    // assign: the kernel of the two assignment passes, valu (k_bivf_assign,
+    // the default) or mfma (k_bivf_assign_mfma); the lists are the same
+    const std::string assign_kind = pm.count("assign") ? pm.at("assign") : "valu";
+    if (assign_kind != "valu" && assign_kind != "mfma")
+        fail(MQVS_ERR_BAD_ARGUMENTS, "index parameter assign `" + assign_kind + "` is not valu or mfma");
+    const bool assign_mfma = assign_kind == "mfma";
+    if (assign_mfma && (int64_t)seg->code_words * 32 >= (1 << 24))
+        fail(MQVS_ERR_NOT_IMPLEMENTED, "assign=mfma over codes of 2^24 or more bits");
     const int metric = pm.count("metric_type") ? binary_metric_of(pm.at("metric_type"), "metric_type") : seg->metric;
     const int64_t n = seg->n;
     if (n >= ((int64_t)1 << 31)) fail(MQVS_ERR_NOT_IMPLEMENTED, "binary index over 2^31 or more rows");
@@ -562,6 +570,15 @@ static mqvs_index *build_binary_impl(mqvs_segment *seg, const char *params) {
         ix->bcent = dalloc<uint32_t>(ix, (size_t)L * cw);
         MQVS_HIP(hipMemsetAsync(ix->bcent, 0, sizeof(uint32_t) * (size_t)L * cw, s));
         TmpBuf assign(sizeof(int32_t) * std::max<int64_t>(n, 1));
+        // assign=mfma: the centroids as 0/1 bytes and their popcounts, expanded again by every pass
+        TmpBuf cplane(assign_mfma ? bin_plane_bytes(L, cw) : 0), cpop(assign_mfma ? sizeof(uint32_t) * round_up(L, 16) : 0);
+        auto assign_rows = [&](const uint32_t *codes, int64_t m) {
+            if (assign_mfma)
+                launch_bivf_assign_mfma(codes, m, cw, ix->bcent, (int)L, cplane.as<uint8_t>(), cpop.as<uint32_t>(),
+                                        assign.as<int32_t>(), s);
+            else
+                launch_bivf_assign(codes, m, cw, ix->bcent, (int)L, assign.as<int32_t>(), s);
+        };
         if (S > 0) {
             // ---- k-majority on a strided sample of the rows
             std::vector<int32_t> sidx(S);
@@ -577,7 +594,7 @@ static mqvs_index *build_binary_impl(mqvs_segment *seg, const char *params) {
             MQVS_HIP(hipGetLastError());
             TmpBuf counts(sizeof(uint32_t) * (size_t)L * cw * 32), members(sizeof(uint32_t) * L);
             for (int it = 0; it < iters; ++it) {
-                launch_bivf_assign(samp.as<uint32_t>(), S, cw, ix->bcent, (int)L, assign.as<int32_t>(), s);
+                assign_rows(samp.as<uint32_t>(), S);
                 MQVS_HIP(hipMemsetAsync(counts.p, 0, sizeof(uint32_t) * (size_t)L * cw * 32, s));
                 MQVS_HIP(hipMemsetAsync(members.p, 0, sizeof(uint32_t) * L, s));
                 launch_bivf_majority(samp.as<uint32_t>(), S, cw, assign.as<int32_t>(), (int)L, counts.as<uint32_t>(),
@@ -588,7 +605,7 @@ static mqvs_index *build_binary_impl(mqvs_segment *seg, const char *params) {
         }
         // ---- every row to its nearest centroid; lists in row order
         if (n > 0) {
-            launch_bivf_assign(seg->codes, n, cw, ix->bcent, (int)L, assign.as<int32_t>(), s);
+            assign_rows(seg->codes, n);
             MQVS_HIP(hipGetLastError());
         }
         finish_index(ix, assign.as<int32_t>(), false, s);

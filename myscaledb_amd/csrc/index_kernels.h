@@ -197,6 +197,11 @@ struct BivfParams {
 };
 void launch_bivf_assign(const uint32_t *codes, int64_t n, int code_words, const uint32_t *cent, int nlist,
                         int32_t *assign, hipStream_t s);
+// the same assignment on the i8 MFMA (kernels_binary_mfma.hip); cplane / cpop:
+// scratch of bin_plane_bytes(nlist, code_words) bytes and nlist rounded up to
+// 16 words for the expanded centroids; code_words * 32 < 2^24
+void launch_bivf_assign_mfma(const uint32_t *codes, int64_t n, int code_words, const uint32_t *cent, int nlist,
+                             uint8_t *cplane, uint32_t *cpop, int32_t *assign, hipStream_t s);
 // counts [nlist][code_words][32] and members [nlist] must be zero
 void launch_bivf_majority(const uint32_t *codes, int64_t m, int code_words, const int32_t *assign, int nlist,
                           uint32_t *counts, uint32_t *members, uint32_t *cent, hipStream_t s);

@@ -58,20 +58,7 @@ __device__ __forceinline__ void bin_popc(const uint4 q, const uint4 y, uint32_t 
     }
 }
 
-// the dense PROBE value of a row: its distance, NaN when the row is not valid
-// (or, Hamming, at distance nbits)
-template <int METRIC>
-__device__ __forceinline__ float bin_probe_value(uint32_t a, uint32_t b, bool valid_row, int nbits) {
-    float raw;
-    bool valid = valid_row;
-    if (METRIC == MQVS_METRIC_HAMMING) {
-        raw = (float)a;
-        valid = valid && (int)a < nbits;
-    } else {
-        raw = a == 0u ? 1.0f : (float)(b - a) / (float)b;
-    }
-    return valid ? raw : __builtin_nanf("");
-}
+// (bin_probe_value, the dense PROBE value of a row: flat_kernels.h)
 
 // row-per-lane form (k_scan_binary's load_row): the lane's row (position pos
 // of a tile ending at r1) into registers, zeros past the tile

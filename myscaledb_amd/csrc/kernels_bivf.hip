@@ -6,7 +6,10 @@
 // list scan computes the final distance: no approximate stage and no re-rank.
 //
 // Build     k_bivf_assign    nearest centroid by Hamming distance, ties to the
-//                            lowest list id (rows of the sample, then all rows)
+//                            lowest list id (rows of the sample, then all rows);
+//                            assign=mfma: k_bivf_assign_mfma, which shares its
+//                            tile body with the batch scan and lives beside
+//                            it in kernels_binary_mfma.hip
 //           k_bivf_count     per (list, bit) member counts (integer atomics:
 //                            order-independent, so the build is deterministic)
 //           k_bivf_majority  centroid bit = 2 ones > members; empty lists keep

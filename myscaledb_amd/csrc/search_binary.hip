@@ -9,11 +9,16 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <string>
 
 #include "workspace.h"
 
 namespace mqvs {
+
+// mqvs_set_binary_batch: calls of nq >= this take the i8 MFMA scan
+// (kernels_binary_mfma.hip) instead of the popcount scan; 0 = never
+static std::atomic<int32_t> g_binary_batch{0};
 
 void search_binary(mqvs_segment *seg, const uint8_t *queries, int nq, int k, int metric, const uint8_t *filter,
                    const uint8_t *exists, int64_t *out_ids, float *out_dist, uint32_t flags,
@@ -90,6 +95,20 @@ void search_binary(mqvs_segment *seg, const uint8_t *queries, int nq, int k, int
     p.cand_cap = cap;
     p.probe = (float *)ws.probe.get(sizeof(float) * (size_t)nq * std::max<int64_t>(P, 1));
     p.probe_ld = P;
+    // the scan kernel of this call: the popcount scan, or (opt-in) the i8 MFMA
+    // scan over the queries expanded to 0/1 bytes -- the same values and
+    // candidates, so everything around the scan is shared
+    const int32_t batch_min = g_binary_batch.load(std::memory_order_relaxed);
+    const bool mfma = batch_min > 0 && nq >= batch_min;
+    BinPlane qexp{};
+    if (mfma) {
+        uint8_t *qplane = (uint8_t *)ws.bin_qplane.get(bin_plane_bytes(nq, seg->code_words));
+        uint32_t *qpop = (uint32_t *)ws.bin_qpop.get(sizeof(uint32_t) * (size_t)round_up(nq, 16));
+        launch_bin_expand(qc, nq, seg->code_words, qplane, qpop, s);
+        MQVS_HIP(hipGetLastError());
+        qexp.plane = qplane;
+        qexp.pop = qpop;
+    }
     auto scan = [&](int64_t b, int64_t e, bool probe, bool strict) {
         if (e <= b) return;
         p.row_begin = b;
@@ -98,7 +117,10 @@ void search_binary(mqvs_segment *seg, const uint8_t *queries, int nq, int k, int
         p.tiles_per_chunk = 0;
         p.tile_rows = tile_rows;
         p.tau_strict = strict ? 1 : 0;
-        launch_scan_binary(p, metric, probe, s);
+        if (mfma)
+            launch_scan_binary_mfma(p, qexp, metric, probe, s);
+        else
+            launch_scan_binary(p, metric, probe, s);
         MQVS_HIP(hipGetLastError());
     };
     constexpr int kOrder = MQVS_METRIC_L2;  // ascending finite values: ord_asc key, (key, row) ties
@@ -138,7 +160,7 @@ void search_binary(mqvs_segment *seg, const uint8_t *queries, int nq, int k, int
     launch_final_select(cand, count, cap, nq, k, kOrder, 0, seg->row_offset, dids, ddist, overflow, large, s);
     MQVS_HIP(hipGetLastError());
     if (timing) MQVS_HIP(hipEventRecord(ws.ev[4], s));
-    st.path = 3;  // binary popcount scan
+    st.path = mfma ? 4 : 3;  // binary scan: i8 MFMA / popcount
     st.probe_rows = P;
     st.main_rows = n - P;
     st.rows_scanned = n;
@@ -164,4 +186,19 @@ void search_binary(mqvs_segment *seg, const uint8_t *queries, int nq, int k, int
 }
 
 }  // namespace mqvs
+
+extern "C" {
+
+int mqvs_set_binary_batch(int32_t min_nq) {
+    if (min_nq < 0) return MQVS_ERR_BAD_ARGUMENTS;
+    mqvs::g_binary_batch.store(min_nq, std::memory_order_relaxed);
+    return MQVS_OK;
+}
+
+int mqvs_binary_batch(int32_t *min_nq) {
+    if (min_nq) *min_nq = mqvs::g_binary_batch.load(std::memory_order_relaxed);
+    return MQVS_OK;
+}
+
+}  // extern "C"
 

@@ -24,6 +24,9 @@ struct Workspace {
     CallIO io;                       // staged inputs and outputs of host-pointer calls
     GBuf qvars, qnorms, qmu, qlam, status, ord, probe, tau, count, cand, overflow, misc, qhi, bq, thr, cand2, count2,
         gcount, goff, glist, large, sticky, surv, recs, flags, p4q, qord;
+    // binary searches on the i8 MFMA route (search_binary.hip): the call's
+    // queries as 0/1 bytes and their popcounts (launch_bin_expand)
+    GBuf bin_qplane, bin_qpop;
     // part-group searches (part_group.hip) keep their own buffers: the
     // per-part searches nested in such a call use the ones above
     GBuf pg_q, pg_qvars, pg_slots, pg_bits, pg_matrix, pg_lists, pg_sort, pg_part;

@@ -76,7 +76,7 @@ size_t Workspace::free_buffers(bool keep_sticky) {
     for (GBuf *x : {&qvars, &qnorms, &qmu, &qlam, &status, &ord, &probe, &tau, &count, &cand, &overflow, &misc, &qhi,
                     &bq, &thr, &cand2, &count2, &gcount, &goff, &glist, &large, &sticky, &surv, &recs, &flags, &p4q,
                     &qord, &pg_q, &pg_qvars, &pg_slots, &pg_bits, &pg_matrix, &pg_lists, &pg_sort, &pg_part, &pg_cdist,
-                    &pg_probes}) {
+                    &pg_probes, &bin_qplane, &bin_qpop}) {
         if (keep_sticky && x == &sticky) continue;
         b += x->cap;
         x->release();

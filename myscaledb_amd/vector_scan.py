@@ -336,6 +336,22 @@ def try_brute_force_search_binary(x, y, d, k, nx, ny, metric):
     return ids, dist
 
 
+def set_binary_batch(min_nq: int) -> int:
+    """mqvs_set_binary_batch: binary brute-force searches of nq >= ``min_nq``
+    take the i8 MFMA scan (same ids, same distance bits); 0 turns the route
+    off (the default).  Returns the previous setting."""
+    prev = binary_batch()
+    check(lib.mqvs_set_binary_batch(int(min_nq)))
+    return prev
+
+
+def binary_batch() -> int:
+    """The current mqvs_set_binary_batch setting (0 = off)."""
+    v = ctypes.c_int32()
+    check(lib.mqvs_binary_batch(ctypes.byref(v)))
+    return int(v.value)
+
+
 def vector_scan_without_index(segment: VectorScanSegment, query_vector, k, metric=None,
                               filter_bitmap=None, row_exists=None, is_batch=False):
     """MergeTreeVSManager::vectorScanWithoutIndex result columns.
