@@ -13,7 +13,7 @@
 //
 // Where the kernels and their launchers live:
 //   kernels_scan.hip     k_scan_small (VALU), k_scan_mfma, k_scan_group, k_scan_group_mfma
-//   kernels_select.hip   k_probe_select, k_cand_tau, k_final_select, k_merge_shards, k_select_group, k_refine
+//   kernels_select.hip   k_probe_select, k_final_select, k_merge_shards, k_select_group, k_refine
 //   kernels_bf16.hip     k_to_bf16, k_max_norm, k_query_bound, the approximate probe select, k_rerank_select
 //   kernels_hi.hip       k_to_hi, k_scan_hi_* (the bf16 pre-filter scans)
 //   kernels_p4.hip       k_scan_p4* (the batch scan at one wave per SIMD), k_ord_planes
@@ -303,8 +303,6 @@ void launch_scan_group_mfma(const ScanParams &base, const GroupSlot *slots, int 
 void launch_probe_select(const float *probe, int64_t P, int64_t ld, int nq, int k, int metric,
                          uint32_t *tau, int *cand_count, Cand *cand, int cand_cap,
                          int64_t row_base, const int32_t *row_list, hipStream_t s);
-void launch_cand_tau(const Cand *cand, const int *cand_count, int cand_cap, int nq, int k,
-                     int metric, uint32_t *tau, const int *overflow_q, hipStream_t s);
 // scratch: null, or 2 kLargeCap uint4 records per query (k > kSortCap)
 void launch_final_select(const Cand *cand, const int *cand_count, int cand_cap, int nq, int k,
                          int metric, int64_t chunk_rows, int64_t id_offset, int64_t *out_ids,

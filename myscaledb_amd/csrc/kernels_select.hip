@@ -50,22 +50,6 @@ __global__ __launch_bounds__(kProbeThreads) void k_probe_select(const float *pro
     });
 }
 
-// Tighten tau for queries whose candidate list overflowed: the k-th key among
-// the `cap` stored candidates (a subset of rows) bounds the true k-th key.
-template <int METRIC>
-__global__ __launch_bounds__(SEL_THREADS) void k_cand_tau(const Cand *cand, const int *cand_count,
-                                                         int cap, int k, uint32_t *tau) {
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t sh[4];
-    const int q = blockIdx.x;
-    if (cand_count[q] <= cap) return;  // uniform per block
-    const Cand *c = cand + (int64_t)q * cap;
-    auto keyof = [&](int64_t i) { return key32<METRIC>(c[i].raw); };
-    const uint32_t th = block_radix_select(keyof, cap, k, hist, sh);
-    if (threadIdx.x == 0 && th < tau[q]) tau[q] = th;
-}
-
-
 // The select of one query's n candidates c[0, n) (the whole workgroup calls
 // it): the body k_final_select and the part-group select share, so the tie
 // order is stated once.  c[i] yields candidate i as a Cand (a list, or a view
@@ -434,18 +418,6 @@ void launch_probe_select(const float *probe, int64_t P, int64_t ld, int nq, int 
                          (probe, P, ld, nq, k, tau, cand_count, cand, cand_cap, row_base, row_list, s));
 }
 
-template <int M>
-static void cand_tau_t(const Cand *cand, const int *cc, int cap, int nq, int k, uint32_t *tau,
-                       hipStream_t s) {
-    hipLaunchKernelGGL(k_cand_tau<M>, dim3(nq), dim3(SEL_THREADS), 0, s, cand, cc, cap, k, tau);
-}
-
-void launch_cand_tau(const Cand *cand, const int *cand_count, int cand_cap, int nq, int k,
-                     int metric, uint32_t *tau, const int *, hipStream_t s) {
-    if (nq <= 0) return;
-    MQVS_DISPATCH_METRIC(metric, cand_tau_t, (cand, cand_count, cand_cap, nq, k, tau, s));
-}
-
 static size_t sort_lds(int n) {
     int N = 1;
     while (N < n) N <<= 1;
@@ -530,7 +502,13 @@ __global__ __launch_bounds__(SEL_THREADS) void k_refine(const Cand *cin, const i
     extern __shared__ Cand s_cand[];
     const int q = blockIdx.x;
     int n = cnt_in[q];
-    if (n > cap) n = cap;  // overflowed lists keep their overflow: count stays > cap
+    // An overflowed list (its lost rows are unknown) stays flagged: its count
+    // stays above cap, so every later reader takes all cap slots.  It is
+    // therefore copied whole -- compacted, the slots past the kept entries
+    // would hold stale records of earlier searches (thresholds from their
+    // keys fall under the k-th key; their rows may lie past this part).
+    const bool over = n > cap;
+    if (over) n = cap;
     const Cand *c = cin + (int64_t)q * cap;
     if (n <= stage) {
         int i = threadIdx.x;
@@ -572,7 +550,9 @@ __global__ __launch_bounds__(SEL_THREADS) void k_refine(const Cand *cin, const i
     for (int i = threadIdx.x; i < n; i += SEL_THREADS) {
         const Cand e = c[i];
         bool take;
-        if (APPROX) {
+        if (over) {
+            take = true;
+        } else if (APPROX) {
             take = (METRIC == MQVS_METRIC_L2) ? (e.raw <= tf) : (e.raw >= tf);
         } else {
             const uint32_t key = key32<METRIC>(e.raw);
@@ -582,8 +562,7 @@ __global__ __launch_bounds__(SEL_THREADS) void k_refine(const Cand *cin, const i
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        // an overflowed input stays flagged as overflowed (its lost rows are unknown)
-        cnt_out[q] = cnt_in[q] > cap ? cnt_in[q] : s_cnt;
+        cnt_out[q] = over ? cnt_in[q] : s_cnt;
         if (APPROX) thr[q] = tf;
         else tau[q] = tk;
     }

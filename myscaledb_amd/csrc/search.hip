@@ -7,8 +7,10 @@
 //   3. probe select      per-query k-th key -> threshold tau; first candidates
 //   4. main scan         rows [P, n), append rows with key <= tau
 //   5. final select      sort candidates by the reference's total order, emit k
-// If a candidate list overflows (adversarial ties), tau is tightened from the
-// stored candidates and the part is re-scanned (rare; counted in the stats).
+// If a candidate list overflows (mass ties; rows ordered by distance to the
+// queries), the stored candidates and tau are discarded and the part is
+// re-scanned from an empty list in short segments with a refinement after
+// each (rescan_on_overflow; counted in the stats).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -211,7 +213,8 @@ struct FlatSearch {
     float *qvars = nullptr;
     int *qmu = nullptr, *qlam = nullptr;
     uint32_t *tau = nullptr;
-    Cand *cand = nullptr;
+    Cand *cand = nullptr, *cand_alt = nullptr;  // the lists; what the refinements compact them into
+    int *count_alt = nullptr;
     float *bq = nullptr, *probe = nullptr;
     uint4 *large = nullptr;
     int32_t *spec_list = nullptr;
@@ -591,8 +594,8 @@ void FlatSearch::run_probe() {
 // probe's threshold is loose, e.g. clustered data)
 void FlatSearch::run_segments() {
     const int64_t align = aligned ? seg->granule : tile_rows;
-    Cand *alt = (Cand *)ws.cand2.get(sizeof(Cand) * (size_t)nq * cap);
-    int *calt = (int *)ws.count2.get(sizeof(int) * nq);
+    cand_alt = (Cand *)ws.cand2.get(sizeof(Cand) * (size_t)nq * cap);
+    count_alt = (int *)ws.count2.get(sizeof(int) * nq);
     // (the batch probe appended nothing: the first segment also covers
     // the probe rows)
     // (a segment of fewer than kMinSegRows rows cannot fill the chip --
@@ -622,10 +625,11 @@ void FlatSearch::run_segments() {
         seg_rows *= tune.growth;
         ++segs;
         if (b < scan_n) {
-            launch_refine(cand, count, cap, nq, k, metric, kind == kScanBf16, bq, tau, (float *)p.thr, alt, calt, s);
+            launch_refine(cand, count, cap, nq, k, metric, kind == kScanBf16, bq, tau, (float *)p.thr, cand_alt,
+                          count_alt, s);
             MQVS_HIP(hipGetLastError());
-            std::swap(cand, alt);
-            std::swap(count, calt);
+            std::swap(cand, cand_alt);
+            std::swap(count, count_alt);
             p.cand = cand;
             p.cand_count = count;
         }
@@ -724,10 +728,12 @@ void FlatSearch::finish_sync() {
         search_stats().rescans += 1;
         return;
     }
-    OverflowRescan r{cand, count, cap, nq, k, metric, tau, overflow, seg->granule, seg->row_offset, out.ids, out.dist,
-                     large};
-    st.rescans = rescan_on_overflow(ws, r, s, [&] {
-        run_scan(p, make_range(0, scan_n, tile_rows, seg->granule, aligned), kind, metric, false, s);
+    OverflowRescan r{cand, cand_alt, count, count_alt, cap, nq, k, metric, tau, overflow, seg->granule,
+                     seg->row_offset, out.ids, out.dist, large, scan_n, aligned ? seg->granule : tile_rows};
+    st.rescans = rescan_on_overflow(ws, r, s, [&](int64_t b, int64_t e, Cand *to, int *to_count) {
+        p.cand = to;
+        p.cand_count = to_count;
+        run_scan(p, make_range(b, e, tile_rows, seg->granule, aligned), kind, metric, false, s);
     });
     if (st.rescans)
         ws.io.finish(out, s);

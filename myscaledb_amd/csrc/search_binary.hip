@@ -131,9 +131,9 @@ void search_binary(mqvs_segment *seg, const uint8_t *queries, int nq, int k, int
     launch_probe_select(p.probe, P, P, nq, k, kOrder, tau, count, cand, cap, 0, nullptr, s);
     MQVS_HIP(hipGetLastError());
     if (timing) MQVS_HIP(hipEventRecord(ws.ev[2], s));
+    Cand *alt = (Cand *)ws.cand2.get(sizeof(Cand) * (size_t)nq * cap);
+    int *calt = (int *)ws.count2.get(sizeof(int) * nq);
     {
-        Cand *alt = (Cand *)ws.cand2.get(sizeof(Cand) * (size_t)nq * cap);
-        int *calt = (int *)ws.count2.get(sizeof(int) * nq);
         // segments grow x4: each refine costs a launch, and appends per
         // segment stay near (growth x k) with the threshold refined
         int64_t b = P, seg_rows = std::max<int64_t>(2 * P, tile_rows);
@@ -174,8 +174,13 @@ void search_binary(mqvs_segment *seg, const uint8_t *queries, int nq, int k, int
         ws.io.finish_begin(out, s);
         MQVS_HIP(hipMemcpyAsync(ws.host_flags, overflow, sizeof(int), hipMemcpyDeviceToHost, s));
         host_wait(s);
-        OverflowRescan r{cand, count, cap, nq, k, kOrder, tau, overflow, 0, seg->row_offset, dids, ddist, large};
-        st.rescans = rescan_on_overflow(ws, r, s, [&] { scan(0, n, false, false); });
+        OverflowRescan r{cand, alt,   count, calt, cap, nq, k, kOrder, tau, overflow, 0, seg->row_offset,
+                         dids, ddist, large, n,    tile_rows};
+        st.rescans = rescan_on_overflow(ws, r, s, [&](int64_t b, int64_t e, Cand *to, int *to_count) {
+            p.cand = to;
+            p.cand_count = to_count;
+            scan(b, e, false, false);
+        });
         if (st.rescans)
             ws.io.finish(out, s);
         else

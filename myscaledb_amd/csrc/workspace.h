@@ -101,14 +101,24 @@ int *sticky_word(Workspace &ws, hipStream_t s);
 // (0: main_ms is the whole span between the probe select and the final select)
 void read_search_times(Workspace &ws, mqvs_search_stats &st, int seg_events);
 
-// The host-driven answer to a candidate-list overflow (more than cap rows at
-// or under the probe threshold; rare): while the overflow word read into
-// ws.host_flags[0] is set, tighten tau from what was kept, re-scan the part
-// inclusively (`rescan`) and select again -- at most 3 times.  Returns the
-// number of re-scans.
+// The host-driven answer to a candidate-list overflow: one main-scan segment
+// held more than cap rows at or under its threshold -- a mass tie, or a part
+// whose rows come ever nearer to the queries, where almost every row passes
+// the threshold of the rows before it.  When the overflow word read into
+// ws.host_flags[0] is set, the lists are emptied, tau is reset to "every row"
+// and the part is scanned once more from position 0, inclusively, in segments
+// of at most cap / 2 positions (`scan(b, e, cand, count)` appends to that
+// list), with an exact refinement after each; then the select again.
+// (Nothing of the overflowed pass is kept, its thresholds included: they
+// came from whichever cap rows happened to be stored.)  A refined list holds
+// the k best rows so far and the rows within the threshold's slack of the
+// k-th (a bound: 2^-16 relative), and a segment adds at most cap / 2 rows, so
+// whichever appends landed first, a list overflows again only when more than
+// cap / 2 rows tie at or near a k-th key: that is the error.  One pass, no
+// loop.  Returns the number of re-scans (0 or 1).
 struct OverflowRescan {
-    Cand *cand;
-    int *count;
+    Cand *cand, *alt;  // the lists, and the buffer the refinements compact them into
+    int *count, *count_alt;
     int cap, nq, k, order;  // order: the metric whose key orders the candidates
     uint32_t *tau;
     int *overflow;
@@ -116,24 +126,34 @@ struct OverflowRescan {
     int64_t *dids;
     float *ddist;
     uint4 *large;
+    int64_t rows, align;  // scan positions [0, rows); a segment's bounds are multiples of align
 };
 template <typename Scan>
-int rescan_on_overflow(Workspace &ws, const OverflowRescan &r, hipStream_t s, Scan &&rescan) {
-    int rescans = 0;
-    while (ws.host_flags[0]) {
-        if (++rescans > 3)
-            fail(MQVS_ERR_LOGICAL, "candidate overflow: more than " + std::to_string(r.cap) +
-                                       " rows tie at the k-th distance");
-        launch_cand_tau(r.cand, r.count, r.cap, r.nq, r.k, r.order, r.tau, nullptr, s);
-        launch_fill2((uint32_t *)r.count, r.nq, 0u, (uint32_t *)r.overflow, 4, 0u, s);
-        rescan();
-        launch_final_select(r.cand, r.count, r.cap, r.nq, r.k, r.order, r.chunk_rows, r.id_offset, r.dids, r.ddist,
-                            r.overflow, r.large, s);
-        MQVS_HIP(hipGetLastError());
-        MQVS_HIP(hipMemcpyAsync(ws.host_flags, r.overflow, sizeof(int), hipMemcpyDeviceToHost, s));
-        host_wait(s);
+int rescan_on_overflow(Workspace &ws, OverflowRescan r, hipStream_t s, Scan &&scan) {
+    if (!ws.host_flags[0]) return 0;
+    launch_fill2((uint32_t *)r.count, r.nq, 0u, (uint32_t *)r.overflow, 4, 0u, s);
+    launch_fill2(r.tau, r.nq, 0xFFFFFFFEu, nullptr, 0, 0u, s);
+    const int64_t seg_rows = std::max<int64_t>(r.align, r.cap / 2 / r.align * r.align);
+    for (int64_t b = 0; b < r.rows; b += seg_rows) {
+        const int64_t e = std::min(r.rows, b + seg_rows);
+        scan(b, e, r.cand, r.count);
+        if (e < r.rows) {
+            launch_refine(r.cand, r.count, r.cap, r.nq, r.k, r.order, false, nullptr, r.tau, nullptr, r.alt,
+                          r.count_alt, s);
+            MQVS_HIP(hipGetLastError());
+            std::swap(r.cand, r.alt);
+            std::swap(r.count, r.count_alt);
+        }
     }
-    return rescans;
+    launch_final_select(r.cand, r.count, r.cap, r.nq, r.k, r.order, r.chunk_rows, r.id_offset, r.dids, r.ddist,
+                        r.overflow, r.large, s);
+    MQVS_HIP(hipGetLastError());
+    MQVS_HIP(hipMemcpyAsync(ws.host_flags, r.overflow, sizeof(int), hipMemcpyDeviceToHost, s));
+    host_wait(s);
+    if (ws.host_flags[0])
+        fail(MQVS_ERR_LOGICAL,
+             "candidate overflow: more than " + std::to_string(r.cap) + " rows tie at the k-th distance");
+    return 1;
 }
 
 }  // namespace mqvs
