@@ -30,15 +30,12 @@
 // search_host.h.
 #pragma once
 
+#include <type_traits>
+
+#include "cand_list.h"  // Cand, the candidate list's contract and its append / read functions
 #include "mqvs_internal.h"
 
 namespace mqvs {
-
-// Candidate record: raw metric value (d for L2, ip for IP/cosine) + local row.
-struct __attribute__((aligned(8))) Cand {
-    float raw;
-    uint32_t row;
-};
 
 // ---------------------------------------------------------------------------
 // Ordering keys.  key32(raw) is a monotone encoding of the primary sort key
@@ -235,6 +232,23 @@ __device__ __forceinline__ float bin_probe_value(uint32_t a, uint32_t b, bool va
         raw = a == 0u ? 1.0f : (float)(b - a) / (float)b;
     }
     return valid ? raw : __builtin_nanf("");
+}
+
+// The code width as a compile-time W4 = code_words / 4 (16-B slices per code)
+// for the binary scans whose lanes read consecutive slices: f gets an
+// integral_constant of 1, 2, 4 or 8, or of 0 for every other quotient (code
+// rows are whole 16-B slices; the quotient is what the launchers always
+// switched on).  Host side, here because the launchers of kernels_binary.hip
+// and kernels_bivf.hip share no other header.
+template <class F>
+inline void with_w4(int code_words, F &&f) {
+    switch (code_words / 4) {
+        case 1: f(std::integral_constant<int, 1>{}); return;
+        case 2: f(std::integral_constant<int, 2>{}); return;
+        case 4: f(std::integral_constant<int, 4>{}); return;
+        case 8: f(std::integral_constant<int, 8>{}); return;
+        default: f(std::integral_constant<int, 0>{}); return;
+    }
 }
 
 // ---------------------------------------------------------------------------

@@ -175,8 +175,7 @@ __global__ __launch_bounds__(kPsThreads) void k_probe_select_wide(const float *p
     // thread held more than kPsKeep of the k best (k 100 of 32768 values:
     // ~0.1 per thread).  Three passes over the row with an LDS atomic per
     // value took 17-27 us at nq 1.
-    bool none = false;
-    uint32_t prefix = 0;
+    uint32_t sel;  // a bound on the k-th key (its low byte set); 0xFFFFFFFE: fewer than k values
     if (k <= kPsKeepMaxK) {
         uint32_t best[kPsKeep];
 #pragma unroll
@@ -196,64 +195,29 @@ __global__ __launch_bounds__(kPsThreads) void k_probe_select_wide(const float *p
 #pragma unroll
         for (int j = 0; j < kPsKeep; ++j) skeys[j * kPsThreads + t] = best[j];
         __syncthreads();
-        const uint32_t sel = block_radix_select_mlp<kPsThreads, 3>([&](int64_t i) { return skeys[i]; },
-                                                                  (int64_t)kPsKeep * kPsThreads, k, hist, sh);
-        none = sel == 0xFFFFFFFEu;
-        prefix = sel & ~0xFFu;
+        sel = block_radix_select_mlp<kPsThreads, 3>([&](int64_t i) { return skeys[i]; },
+                                                   (int64_t)kPsKeep * kPsThreads, k, hist, sh);
     } else {
-        // large k: three passes over the row; the bound takes the low byte set
-        // (an upper bound on the k-th key, as block_radix_select<3>)
-        uint32_t mask = 0, kk = (uint32_t)k;
-        for (int pass = 0; pass < 3; ++pass) {
-            const int shift = 24 - 8 * pass;
-            if (t < 256) hist[t] = 0;
-            __syncthreads();
-            RunHist rh;
-            for_each_f4<kPsThreads>(row, P, [&](int64_t, float raw) {
-                const uint32_t key = okey<METRIC>(raw);
-                if (key != 0xFFFFFFFFu && (key & mask) == prefix) rh.add(hist, (key >> shift) & 255u);
-            });
-            rh.flush(hist);
-            __syncthreads();
-            hist_pick(hist, kk, pass == 0, sh);
-            __syncthreads();
-            if (sh[0]) {
-                none = true;
-                break;
-            }
-            prefix |= sh[1] << shift;
-            mask |= 255u << shift;
-            kk -= sh[2];
-            __syncthreads();
-        }
+        // large k: three passes over the row
+        sel = radix_passes<kPsThreads, 3>(
+            [&](auto visit) {
+                for_each_f4<kPsThreads>(row, P, [&](int64_t, float raw) { visit(okey<METRIC>(raw)); });
+            },
+            k, hist, sh);
     }
     float tt;
-    if (none)
+    if (sel == 0xFFFFFFFEu)
         tt = (METRIC == MQVS_METRIC_L2) ? __builtin_inff() : -__builtin_inff();
     else
-        tt = widen<METRIC>(okey_bound_value<METRIC>(prefix | 0xFFu), bq[q]);
+        tt = widen<METRIC>(okey_bound_value<METRIC>(sel), bq[q]);
     if (t == 0) thr[q] = tt;
     if (!cand) return;  // (the batch probe's maxima: threshold only)
-    const int lane = t & 63;
+    // one counter atomic per wave and value step
     for_each_f4<kPsThreads>(row, P, [&](int64_t i, float raw) {
         const bool take = (METRIC == MQVS_METRIC_L2) ? (raw <= tt) : (raw >= tt);
-        // one counter atomic per wave and value step (the lanes that take
-        // get consecutive slots)
-        const uint64_t m = __ballot(take);
-        if (m == 0) return;
-        const int leader = __ffsll((long long)m) - 1;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(&cand_count[q], __popcll(m));
-        base = __shfl(base, leader);
-        if (take) {
-            const int pos = base + __popcll(m & ((1ull << lane) - 1));
-            if (pos < cap) {
-                Cand c;
-                c.raw = raw;
-                c.row = row_list ? (uint32_t)row_list[i] : (uint32_t)i;
-                cand[(int64_t)q * cap + pos] = c;
-            }
-        }
+        // (only takers read the gather list)
+        cand_append_wave(cand, cand_count, cap, q, take, raw,
+                         (take && row_list) ? (uint32_t)row_list[i] : (uint32_t)i);
     });
 }
 
@@ -290,11 +254,9 @@ __global__ __launch_bounds__(SEL_THREADS) void k_survivors(ScanParams p, const f
     __shared__ uint32_t sh[4];
     __shared__ int s_cnt;
     const int q = blockIdx.x;
-    int n = p.cand_count[q];
-    if (n > p.cand_cap) {
-        if (threadIdx.x == 0) atomicOr(overflow, 1);
-        n = p.cand_cap;
-    }
+    bool over;
+    const int n = cand_len(p.cand_count, p.cand_cap, q, over);
+    if (over && threadIdx.x == 0) atomicOr(overflow, 1);
     const Cand *c = p.cand + (int64_t)q * p.cand_cap;
     // (a bound on the k-th key is enough: 3 radix passes, block_radix_select;
     // k <= 256: over the threads' 4 smallest keys, kept_kth_bound)

@@ -194,6 +194,8 @@ __global__ __launch_bounds__(256) void k_scan_binary(ScanParams p) {
                         take = p.tau_strict ? key < tau : key <= tau;
                     }
                 }
+                // (cand_append_wave, cand_list.h, kept open-coded: behind the
+                // function this kernel compiles to another instruction stream)
                 const unsigned long long m = __ballot(take);
                 if (m == 0) continue;
                 const int lane = t & 63;
@@ -203,12 +205,7 @@ __global__ __launch_bounds__(256) void k_scan_binary(ScanParams p) {
                 base = __shfl(base, leader);
                 if (take) {
                     const int slot = base + __popcll(m & ((1ull << lane) - 1ull));
-                    if (slot < p.cand_cap) {
-                        Cand c;
-                        c.raw = raw;
-                        c.row = (uint32_t)row;
-                        p.cand[(int64_t)j * p.cand_cap + slot] = c;
-                    }
+                    cand_store(p.cand, p.cand_cap, j, slot, raw, (uint32_t)row);
                 }
             }
         }
@@ -298,22 +295,7 @@ __global__ __launch_bounds__(256) void k_scan_binary_co(ScanParams p) {
                         take = p.tau_strict ? key < tau : key <= tau;
                     }
                 }
-                const unsigned long long m = __ballot(take);
-                if (m == 0) continue;
-                const int lane = t & 63;
-                const int leader = __ffsll((long long)m) - 1;
-                int cbase = 0;
-                if (lane == leader) cbase = atomicAdd(&p.cand_count[jj], __popcll(m));
-                cbase = __shfl(cbase, leader);
-                if (take) {
-                    const int slot = cbase + __popcll(m & ((1ull << lane) - 1ull));
-                    if (slot < p.cand_cap) {
-                        Cand c;
-                        c.raw = raw;
-                        c.row = (uint32_t)row;
-                        p.cand[(int64_t)jj * p.cand_cap + slot] = c;
-                    }
-                }
+                cand_append_wave(p.cand, p.cand_count, p.cand_cap, jj, take, raw, (uint32_t)row);
             }
         }
     }
@@ -327,22 +309,29 @@ static int64_t bin_grid_cap() {
     return cap;
 }
 
+// The form of a binary scan, per-part or grouped: launch(W4, REG) with W4 in
+// {1, 2, 4, 8} for the coalesced kernel (small batches of those code widths),
+// else W4 = 0 for the row-per-lane kernel, REG when its rows fit the registers.
+template <class Launch>
+static void bin_scan_form(const ScanParams &p, Launch &&launch) {
+    const bool co = p.nq <= 8 && !tune_env("MQVS_BIN_NOCO");
+    with_w4(co ? p.code_words : 0, [&](auto w4) {
+        if (w4 > 0 || p.code_words <= 32)
+            launch(w4, std::true_type{});
+        else
+            launch(w4, std::false_type{});
+    });
+}
+
 template <int METRIC, bool PROBE>
 static void scan_binary_t(const ScanParams &p, hipStream_t s) {
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(p.tiles, bin_grid_cap()));
-    if (p.nq <= 8 && !tune_env("MQVS_BIN_NOCO")) {
-        switch (p.code_words / 4) {
-            case 1: hipLaunchKernelGGL((k_scan_binary_co<METRIC, PROBE, 1>), dim3(grid), dim3(256), 0, s, p); return;
-            case 2: hipLaunchKernelGGL((k_scan_binary_co<METRIC, PROBE, 2>), dim3(grid), dim3(256), 0, s, p); return;
-            case 4: hipLaunchKernelGGL((k_scan_binary_co<METRIC, PROBE, 4>), dim3(grid), dim3(256), 0, s, p); return;
-            case 8: hipLaunchKernelGGL((k_scan_binary_co<METRIC, PROBE, 8>), dim3(grid), dim3(256), 0, s, p); return;
-            default: break;
-        }
-    }
-    if (p.code_words <= 32)
-        hipLaunchKernelGGL((k_scan_binary<METRIC, PROBE, true>), dim3(grid), dim3(256), 0, s, p);
-    else
-        hipLaunchKernelGGL((k_scan_binary<METRIC, PROBE, false>), dim3(grid), dim3(256), 0, s, p);
+    bin_scan_form(p, [&](auto w4, auto reg) {
+        if constexpr (w4 > 0)
+            hipLaunchKernelGGL((k_scan_binary_co<METRIC, PROBE, w4>), dim3(grid), dim3(256), 0, s, p);
+        else
+            hipLaunchKernelGGL((k_scan_binary<METRIC, PROBE, reg>), dim3(grid), dim3(256), 0, s, p);
+    });
 }
 
 void launch_scan_binary(const ScanParams &p, int metric, bool probe, hipStream_t s) {
@@ -481,34 +470,14 @@ static void scan_group_binary_t(const ScanParams &p, const GroupSlot *slots, int
                                 hipStream_t s) {
     const int64_t grid = tiles < 4096 ? tiles : 4096;
     if (grid < 1) return;
-    // the form scan_binary_t chooses for this nq and code width
-    if (p.nq <= 8 && !tune_env("MQVS_BIN_NOCO")) {
-        switch (p.code_words / 4) {
-            case 1:
-                hipLaunchKernelGGL((k_scan_group_binary_co<METRIC, 1>), dim3((unsigned)grid), dim3(256), 0, s, p, slots,
-                                   nslots, tiles);
-                return;
-            case 2:
-                hipLaunchKernelGGL((k_scan_group_binary_co<METRIC, 2>), dim3((unsigned)grid), dim3(256), 0, s, p, slots,
-                                   nslots, tiles);
-                return;
-            case 4:
-                hipLaunchKernelGGL((k_scan_group_binary_co<METRIC, 4>), dim3((unsigned)grid), dim3(256), 0, s, p, slots,
-                                   nslots, tiles);
-                return;
-            case 8:
-                hipLaunchKernelGGL((k_scan_group_binary_co<METRIC, 8>), dim3((unsigned)grid), dim3(256), 0, s, p, slots,
-                                   nslots, tiles);
-                return;
-            default: break;
-        }
-    }
-    if (p.code_words <= 32)
-        hipLaunchKernelGGL((k_scan_group_binary<METRIC, true>), dim3((unsigned)grid), dim3(256), 0, s, p, slots, nslots,
-                           tiles);
-    else
-        hipLaunchKernelGGL((k_scan_group_binary<METRIC, false>), dim3((unsigned)grid), dim3(256), 0, s, p, slots,
-                           nslots, tiles);
+    bin_scan_form(p, [&](auto w4, auto reg) {
+        if constexpr (w4 > 0)
+            hipLaunchKernelGGL((k_scan_group_binary_co<METRIC, w4>), dim3((unsigned)grid), dim3(256), 0, s, p, slots,
+                               nslots, tiles);
+        else
+            hipLaunchKernelGGL((k_scan_group_binary<METRIC, reg>), dim3((unsigned)grid), dim3(256), 0, s, p, slots,
+                               nslots, tiles);
+    });
 }
 
 void launch_scan_group_binary(const ScanParams &base, const GroupSlot *slots, int nslots, int64_t tiles, int metric,

@@ -324,17 +324,9 @@ __global__ __launch_bounds__(256, NB == kBmNB ? 1 : 2) void k_scan_binary_mfma(S
                             const uint32_t key = ord_asc(raw);
                             take = take && (p.tau_strict ? key < tauv[nb] : key <= tauv[nb]);
                         }
-                        if (take) {
-                            // hits are rare after the probe: a slot per hit
-                            // (the order inside a list is unspecified)
-                            const int slot = atomicAdd(&p.cand_count[j], 1);
-                            if (slot < p.cand_cap) {
-                                Cand cd;
-                                cd.raw = raw;
-                                cd.row = (uint32_t)pos;
-                                p.cand[(int64_t)j * p.cand_cap + slot] = cd;
-                            }
-                        }
+                        // hits are rare after the probe: a slot per hit
+                        // (the order inside a list is unspecified)
+                        if (take) cand_append_one(p.cand, p.cand_count, p.cand_cap, j, raw, (uint32_t)pos);
                     }
                 }
             }

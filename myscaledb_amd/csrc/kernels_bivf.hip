@@ -265,6 +265,8 @@ __device__ inline void bivf_emit(const BivfParams &p, int q, bool lead, int64_t 
             raw = a == 0u ? 1.0f : (float)(b - a) / (float)b;
         }
     }
+    // (cand_append_wave, cand_list.h, kept open-coded: behind the function the
+    // W4 = 1 scans compile with other registers)
     const unsigned long long m = __ballot(take);
     if (m == 0) return;
     const int lane = threadIdx.x & 63;
@@ -272,15 +274,7 @@ __device__ inline void bivf_emit(const BivfParams &p, int q, bool lead, int64_t 
     int base = 0;
     if (lane == leader) base = atomicAdd(&p.cand_count[q], __popcll(m));
     base = __shfl(base, leader);
-    if (take) {
-        const int slot = base + __popcll(m & ((1ull << lane) - 1ull));
-        if (slot < p.cand_cap) {
-            Cand c;
-            c.raw = raw;
-            c.row = row;
-            p.cand[(int64_t)q * p.cand_cap + slot] = c;
-        }
-    }
+    if (take) cand_store(p.cand, p.cand_cap, q, base + __popcll(m & ((1ull << lane) - 1ull)), raw, row);
 }
 
 // W4 = 1, 2, 4, 8: lanes read consecutive 16-B slices of the list (fully
@@ -355,13 +349,9 @@ __global__ __launch_bounds__(256) void k_bivf_scan(BivfParams p) {
 
 template <int METRIC>
 static void bivf_scan_t(const BivfParams &p, int grid, hipStream_t s) {
-    switch (p.code_words / 4) {
-        case 1: hipLaunchKernelGGL((k_bivf_scan<METRIC, 1>), dim3(grid), dim3(256), 0, s, p); return;
-        case 2: hipLaunchKernelGGL((k_bivf_scan<METRIC, 2>), dim3(grid), dim3(256), 0, s, p); return;
-        case 4: hipLaunchKernelGGL((k_bivf_scan<METRIC, 4>), dim3(grid), dim3(256), 0, s, p); return;
-        case 8: hipLaunchKernelGGL((k_bivf_scan<METRIC, 8>), dim3(grid), dim3(256), 0, s, p); return;
-        default: hipLaunchKernelGGL((k_bivf_scan<METRIC, 0>), dim3(grid), dim3(256), 0, s, p); return;
-    }
+    with_w4(p.code_words, [&](auto w4) {
+        hipLaunchKernelGGL((k_bivf_scan<METRIC, w4>), dim3(grid), dim3(256), 0, s, p);
+    });
 }
 
 // stats[0] records written, [1] non-empty work items, [2] list-plane bytes of
@@ -487,16 +477,10 @@ __global__ __launch_bounds__(256) void k_bivf_group_scan(BivfParams base, const 
 template <int METRIC>
 static void bivf_group_scan_t(const BivfParams &p, const BivfGroupSlot *slots, int nslots, int64_t items, int *count,
                               int grid, hipStream_t s) {
-#define MQVS_BIVF_GROUP_SCAN(W)                                                                                 \
-    hipLaunchKernelGGL((k_bivf_group_scan<METRIC, W>), dim3(grid), dim3(256), 0, s, p, slots, nslots, items, count)
-    switch (p.code_words / 4) {
-        case 1: MQVS_BIVF_GROUP_SCAN(1); return;
-        case 2: MQVS_BIVF_GROUP_SCAN(2); return;
-        case 4: MQVS_BIVF_GROUP_SCAN(4); return;
-        case 8: MQVS_BIVF_GROUP_SCAN(8); return;
-        default: MQVS_BIVF_GROUP_SCAN(0); return;
-    }
-#undef MQVS_BIVF_GROUP_SCAN
+    with_w4(p.code_words, [&](auto w4) {
+        hipLaunchKernelGGL((k_bivf_group_scan<METRIC, w4>), dim3(grid), dim3(256), 0, s, p, slots, nslots, items,
+                           count);
+    });
 }
 
 void launch_bivf_group_coarse(const BivfGroupSlot *slots, int nslots, int64_t ctiles, int code_words,

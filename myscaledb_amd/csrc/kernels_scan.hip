@@ -46,22 +46,7 @@ __device__ inline void emit_wave(const ScanParams &p, int j, int64_t pos, int64_
     }
     const uint32_t key = key32<METRIC>(raw);
     const bool take = have && valid && key != 0xFFFFFFFFu && key <= p.tau[j];
-    const unsigned long long m = __ballot(take);
-    if (m == 0) return;
-    const int lane = threadIdx.x & 63;
-    const int leader = __ffsll((long long)m) - 1;
-    int base = 0;
-    if (lane == leader) base = atomicAdd(&p.cand_count[j], __popcll(m));
-    base = __shfl(base, leader);
-    if (take) {
-        const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-        if (pos < p.cand_cap) {
-            Cand c;
-            c.raw = raw;
-            c.row = (uint32_t)row;
-            p.cand[(int64_t)j * p.cand_cap + pos] = c;
-        }
-    }
+    cand_append_wave(p.cand, p.cand_count, p.cand_cap, j, take, raw, (uint32_t)row);
 }
 
 template <int METRIC, bool PROBE>
@@ -70,15 +55,8 @@ __device__ inline void emit(const ScanParams &p, int j, int64_t pos, int64_t row
         p.probe[(int64_t)j * p.probe_ld + (pos - p.row_begin)] = valid ? raw : nan_f();
     } else if (valid) {
         const uint32_t key = key32<METRIC>(raw);
-        if (key != 0xFFFFFFFFu && key <= p.tau[j]) {
-            const int pos = atomicAdd(&p.cand_count[j], 1);
-            if (pos < p.cand_cap) {
-                Cand c;
-                c.raw = raw;
-                c.row = (uint32_t)row;
-                p.cand[(int64_t)j * p.cand_cap + pos] = c;
-            }
-        }
+        if (key != 0xFFFFFFFFu && key <= p.tau[j])
+            cand_append_one(p.cand, p.cand_count, p.cand_cap, j, raw, (uint32_t)row);
     }
 }
 

@@ -37,17 +37,48 @@ __global__ __launch_bounds__(kProbeThreads) void k_probe_select(const float *pro
     if (threadIdx.x == 0) tau[q] = th;
     for_each_f4<kProbeThreads>(row, P, [&](int64_t i, float raw) {
         const uint32_t key = key32<METRIC>(raw);
-        if (key != 0xFFFFFFFFu && key <= th) {
-            const int pos = atomicAdd(&cand_count[q], 1);
-            if (pos < cap) {
-                Cand c;
-                c.raw = raw;
-                // probe column = scan position; gather mode maps it to the row
-                c.row = row_list ? (uint32_t)row_list[row_base + i] : (uint32_t)(row_base + i);
-                cand[(int64_t)q * cap + pos] = c;
-            }
-        }
+        // probe column = scan position; gather mode maps it to the row
+        if (key != 0xFFFFFFFFu && key <= th)
+            cand_append_one(cand, cand_count, cap, q, raw,
+                            row_list ? (uint32_t)row_list[row_base + i] : (uint32_t)(row_base + i));
     });
+}
+
+// block_radix_select with the pass loop (radix_passes, select_common.h)
+// written out, for final_select_body and k_refine's k > 256 branch.  Kept:
+// over the shared loop both compiled to other instruction streams and, at
+// k 1000 (10M x 768, parent and branch alternating), k_final_select took 145 us
+// instead of 141 and k_refine 40.7 instead of 40.0; with this copy both are
+// back (a library carrying the parent's kernels confirms neither is placement).
+template <int PASSES = 4, typename KeyFn>
+__device__ inline uint32_t final_radix_select(KeyFn keyof, int64_t count, int k, uint32_t *hist, uint32_t *sh) {
+    const int t = threadIdx.x;
+    uint32_t prefix = 0, mask = 0, kk = (uint32_t)k;
+    for (int pass = 0; pass < PASSES; ++pass) {
+        const int shift = 24 - 8 * pass;
+        for (int i = t; i < 256; i += SEL_THREADS) hist[i] = 0;
+        __syncthreads();
+        RunHist rh;
+        for (int64_t i = t; i < count; i += SEL_THREADS) {
+            const uint32_t key = keyof(i);
+            if (key == 0xFFFFFFFFu) continue;
+            if ((key & mask) != prefix) continue;
+            rh.add(hist, (key >> shift) & 255u);
+        }
+        rh.flush(hist);
+        __syncthreads();
+        hist_pick(hist, kk, pass == 0, sh);  // fewer than k valid on pass 0: sh[0] = done
+        __syncthreads();
+        if (sh[0]) {
+            __syncthreads();
+            return 0xFFFFFFFEu;
+        }
+        prefix |= sh[1] << shift;
+        mask |= 255u << shift;
+        kk -= sh[2];
+        __syncthreads();
+    }
+    return PASSES == 4 ? prefix : prefix | (0xFFFFFFFFu >> (8 * PASSES));
 }
 
 // The select of one query's n candidates c[0, n) (the whole workgroup calls
@@ -85,7 +116,7 @@ __device__ __forceinline__ void final_select_body(const CandAt c, const int n, i
     } else {
         // long list: k-th primary key first, then sort only key <= it (k + ties)
         auto keyof = [&](int64_t i) { return key32<METRIC>(c[i].raw); };
-        const uint32_t th = block_radix_select(keyof, n, k, hist, sh);
+        const uint32_t th = final_radix_select(keyof, n, k, hist, sh);
         // rows tying at the k-th key rank by row (L2 / IP / binary: the key
         // then the row is the whole order), so when more than kSortCap rows
         // reach the k-th key only the smallest rows of the tie are kept (the
@@ -131,7 +162,7 @@ __device__ __forceinline__ void final_select_body(const CandAt c, const int n, i
                     const Cand e = c[i];
                     return key32<METRIC>(e.raw) == th ? e.row : 0xFFFFFFFFu;
                 };
-                rth = block_radix_select(rowof, n, k - nbelow, hist, sh);
+                rth = final_radix_select(rowof, n, k - nbelow, hist, sh);
             }
         }
         auto tie_kept = [&](const Cand &e) {
@@ -162,12 +193,12 @@ __device__ __forceinline__ void final_select_body(const CandAt c, const int n, i
             // one radix select per level, and the gather again: exactly k
             auto tied = [&](const Cand &e) { return key32<METRIC>(e.raw) == th; };
             int kk = k - count_if([&](const Cand &e) { return key32<METRIC>(e.raw) < th; });
-            yth = block_radix_select([&](int64_t i) { return tied(c[i]) ? chunk_of(c[i]) : 0xFFFFFFFFu; }, n, kk, hist, sh);
+            yth = final_radix_select([&](int64_t i) { return tied(c[i]) ? chunk_of(c[i]) : 0xFFFFFFFFu; }, n, kk, hist, sh);
             kk -= count_if([&](const Cand &e) { return tied(e) && chunk_of(e) < yth; });
             auto in_y = [&](const Cand &e) { return tied(e) && chunk_of(e) == yth; };
-            zth = block_radix_select([&](int64_t i) { return in_y(c[i]) ? ~ord_asc(c[i].raw) : 0xFFFFFFFFu; }, n, kk, hist, sh);
+            zth = final_radix_select([&](int64_t i) { return in_y(c[i]) ? ~ord_asc(c[i].raw) : 0xFFFFFFFFu; }, n, kk, hist, sh);
             kk -= count_if([&](const Cand &e) { return in_y(e) && ~ord_asc(e.raw) < zth; });
-            rth = block_radix_select(
+            rth = final_radix_select(
                 [&](int64_t i) { return in_y(c[i]) && ~ord_asc(c[i].raw) == zth ? c[i].row : 0xFFFFFFFFu; }, n, kk, hist, sh);
             __syncthreads();
         }
@@ -227,6 +258,8 @@ __global__ __launch_bounds__(SEL_THREADS) void k_final_select(const Cand *cand,
     __shared__ int s_cnt;
     const int q = blockIdx.x;
     uint4 *g = scratch ? scratch + (int64_t)q * 2 * kLargeCap : nullptr;
+    // (cand_len, cand_list.h, written out: with final_radix_select it keeps
+    // this kernel's instruction stream as it was)
     int n = cand_count[q];
     if (n > cap) {
         if (threadIdx.x == 0) atomicOr(overflow, 1);
@@ -281,11 +314,9 @@ __global__ __launch_bounds__(SEL_THREADS) void k_bivf_group_select(const Cand *c
     __shared__ int s_cnt;
     const int q = blockIdx.x % nq;
     const BivfGroupSlot &g = slots[blockIdx.x / nq];
-    int n = count[g.count0 + q];
-    if (n > g.cap) {
-        if (threadIdx.x == 0) atomicOr(overflow, 1);
-        n = g.cap;
-    }
+    bool over;
+    const int n = cand_len(count + g.count0, g.cap, q, over);
+    if (over && threadIdx.x == 0) atomicOr(overflow, 1);
     const int64_t o = ((int64_t)g.part * nq + q) * k;
     final_select_body<MQVS_METRIC_L2>(cand + g.cand0 + (int64_t)q * g.cap, n, k, 0, g.row_offset, list_ids + o,
                                       list_dist + o, overflow, (uint4 *)nullptr, recs, hist, sh, &s_cnt);
@@ -501,14 +532,14 @@ __global__ __launch_bounds__(SEL_THREADS) void k_refine(const Cand *cin, const i
     __shared__ int s_cnt;
     extern __shared__ Cand s_cand[];
     const int q = blockIdx.x;
-    int n = cnt_in[q];
-    // An overflowed list (its lost rows are unknown) stays flagged: its count
-    // stays above cap, so every later reader takes all cap slots.  It is
-    // therefore copied whole -- compacted, the slots past the kept entries
-    // would hold stale records of earlier searches (thresholds from their
-    // keys fall under the k-th key; their rows may lie past this part).
-    const bool over = n > cap;
-    if (over) n = cap;
+    // An overflowed list (its lost rows are unknown) stays flagged (the
+    // contract, cand_list.h): its count stays above cap, so every later reader
+    // takes all cap slots.  It is therefore copied whole -- compacted, the
+    // slots past the kept entries would hold stale records of earlier searches
+    // (thresholds from their keys fall under the k-th key; their rows may lie
+    // past this part).
+    bool over;
+    const int n = cand_len(cnt_in, cap, q, over);
     const Cand *c = cin + (int64_t)q * cap;
     if (n <= stage) {
         int i = threadIdx.x;
@@ -531,7 +562,7 @@ __global__ __launch_bounds__(SEL_THREADS) void k_refine(const Cand *cin, const i
     if (APPROX) {
         auto keyof = [&](int64_t i) { return okey<METRIC>(c[i].raw); };
         const uint32_t th = kept ? kept_kth_bound<SEL_THREADS, 4>(keyof, n, k, skeys, hist, sh)
-                                 : block_radix_select<3>(keyof, n, k, hist, sh);  // (a bound: 3 passes)
+                                 : final_radix_select<3>(keyof, n, k, hist, sh);  // (a bound: 3 passes)
         tf = thr[q];
         if (th != 0xFFFFFFFEu) {
             const float w = widen<METRIC>(okey_bound_value<METRIC>(th), bq[q]);
@@ -540,7 +571,7 @@ __global__ __launch_bounds__(SEL_THREADS) void k_refine(const Cand *cin, const i
     } else {
         auto keyof = [&](int64_t i) { return key32<METRIC>(c[i].raw); };
         const uint32_t th = kept ? kept_kth_bound<SEL_THREADS, 4>(keyof, n, k, skeys, hist, sh)
-                                 : block_radix_select<3>(keyof, n, k, hist, sh);
+                                 : final_radix_select<3>(keyof, n, k, hist, sh);
         tk = tau[q];
         if (th < tk) tk = th;
     }

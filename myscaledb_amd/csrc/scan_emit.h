@@ -21,15 +21,8 @@ __device__ inline void emit_approx(const ScanParams &p, int j, int64_t pos, int6
     if constexpr (!AGG) {
         if (!valid) return;
         const float t = p.thr[j];
-        if ((METRIC == MQVS_METRIC_L2) ? (raw <= t) : (raw >= t)) {
-            const int slot = atomicAdd(&p.cand_count[j], 1);
-            if (slot < p.cand_cap) {
-                Cand c;
-                c.raw = raw;
-                c.row = (uint32_t)row;
-                p.cand[(int64_t)j * p.cand_cap + slot] = c;
-            }
-        }
+        if ((METRIC == MQVS_METRIC_L2) ? (raw <= t) : (raw >= t))
+            cand_append_one(p.cand, p.cand_count, p.cand_cap, j, raw, (uint32_t)row);
         return;
     }
     const bool take = valid && ((METRIC == MQVS_METRIC_L2) ? (raw <= p.thr[j]) : (raw >= p.thr[j]));
@@ -38,6 +31,8 @@ __device__ inline void emit_approx(const ScanParams &p, int j, int64_t pos, int6
     // loose threshold early in a scan -- every taker of a wave hits the same
     // counter, and per-lane atomics on it serialised the first main segment
     // of a 1 %-selective gathered scan (6.6k appends: 129 us for 66k rows).
+    // (Open-coded here, not in cand_list.h: behind a function the k_scan_hi
+    // kernels compile to other instruction streams.)
     uint64_t pend = __ballot(take);
     if (pend == 0) return;
     const int lane = (int)__lane_id();
@@ -49,15 +44,8 @@ __device__ inline void emit_approx(const ScanParams &p, int j, int64_t pos, int6
         int base = 0;
         if (lane == leader) base = atomicAdd(&p.cand_count[jl], (int)__popcll(same));
         base = __shfl(base, leader);
-        if (mine) {
-            const int slot = base + (int)__popcll(same & ((1ull << lane) - 1ull));
-            if (slot < p.cand_cap) {
-                Cand c;
-                c.raw = raw;
-                c.row = (uint32_t)row;
-                p.cand[(int64_t)j * p.cand_cap + slot] = c;
-            }
-        }
+        if (mine)
+            cand_store(p.cand, p.cand_cap, j, base + (int)__popcll(same & ((1ull << lane) - 1ull)), raw, (uint32_t)row);
         pend &= ~same;
     }
 }

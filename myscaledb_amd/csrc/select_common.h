@@ -1,5 +1,6 @@
-// select_common.h -- block-wide radix select, float-row visitor and LDS bitonic
-// sort shared by the selection kernels (kernels_select.hip, kernels_bf16.hip).
+// select_common.h -- block-wide radix select (one pass loop, radix_passes, and
+// its feeds), float-row visitor and LDS bitonic sort shared by the selection
+// kernels (kernels_select.hip, kernels_bf16.hip, the index picks and selects).
 #pragma once
 #include "flat_kernels.h"
 
@@ -72,28 +73,29 @@ __device__ inline void hist_pick(const uint32_t *hist, uint32_t kk, bool first, 
     }
 }
 
-// k-th smallest valid key (1-based rank k) among `count` values produced by
-// load(i); 0xFFFFFFFE when fewer than k values are valid.  Block-wide.
+// The radix select's pass loop, block-wide (NT threads): the k-th smallest
+// valid key (1-based rank k) of the block's keys, 8 bits per pass from the
+// top; 0xFFFFFFFE when fewer than k keys are valid.  feed(visit) calls
+// visit(key) for each of the block's keys (its thread's share) on every pass;
+// 0xFFFFFFFF keys are not valid.  hist[256], sh[4]: LDS words.
 // PASSES = 3 (thresholds only): the top 24 bits of the k-th key, the low byte
 // set -- an upper bound on the k-th key (every key <= it passes a "<= bound"
 // test, so a threshold built from it keeps every row the exact one keeps;
 // 2^-16 relative looser) without the fourth histogram pass.
-template <int PASSES = 4, typename KeyFn>
-__device__ inline uint32_t block_radix_select(KeyFn keyof, int64_t count, int k, uint32_t *hist,
-                                       uint32_t *sh) {
+template <int NT, int PASSES, typename Feed>
+__device__ inline uint32_t radix_passes(Feed feed, int k, uint32_t *hist, uint32_t *sh) {
     const int t = threadIdx.x;
     uint32_t prefix = 0, mask = 0, kk = (uint32_t)k;
     for (int pass = 0; pass < PASSES; ++pass) {
         const int shift = 24 - 8 * pass;
-        for (int i = t; i < 256; i += SEL_THREADS) hist[i] = 0;
+        for (int i = t; i < 256; i += NT) hist[i] = 0;
         __syncthreads();
         RunHist rh;
-        for (int64_t i = t; i < count; i += SEL_THREADS) {
-            const uint32_t key = keyof(i);
-            if (key == 0xFFFFFFFFu) continue;
-            if ((key & mask) != prefix) continue;
-            rh.add(hist, (key >> shift) & 255u);
-        }
+        // (the prefix test first: in this order no selection kernel takes more
+        // registers than it did with a pass loop of its own)
+        feed([&](uint32_t key) {
+            if ((key & mask) == prefix && key != 0xFFFFFFFFu) rh.add(hist, (key >> shift) & 255u);
+        });
         rh.flush(hist);
         __syncthreads();
         hist_pick(hist, kk, pass == 0, sh);  // fewer than k valid on pass 0: sh[0] = done
@@ -110,45 +112,34 @@ __device__ inline uint32_t block_radix_select(KeyFn keyof, int64_t count, int k,
     return PASSES == 4 ? prefix : prefix | (0xFFFFFFFFu >> (8 * PASSES));
 }
 
-// block_radix_select with the bucket search in parallel and 4 keys in
-// flight per thread (keyof(i) may read global memory).
+// radix_passes over the `count` keys keyof(i), one in flight per thread.
+template <int PASSES = 4, typename KeyFn>
+__device__ inline uint32_t block_radix_select(KeyFn keyof, int64_t count, int k, uint32_t *hist,
+                                       uint32_t *sh) {
+    return radix_passes<SEL_THREADS, PASSES>(
+        [&](auto visit) {
+            for (int64_t i = threadIdx.x; i < count; i += SEL_THREADS) visit(keyof(i));
+        },
+        k, hist, sh);
+}
+
+// block_radix_select with 4 keys in flight per thread (keyof(i) may read
+// global memory).
 template <int NT = SEL_THREADS, int PASSES = 4, typename KeyFn>
 __device__ inline uint32_t block_radix_select_mlp(KeyFn keyof, int64_t count, int k, uint32_t *hist, uint32_t *sh) {
-    constexpr int SEL_THREADS = NT;  // block size of the caller
-    const int t = threadIdx.x;
-    uint32_t prefix = 0, mask = 0, kk = (uint32_t)k;
-    for (int pass = 0; pass < PASSES; ++pass) {
-        const int shift = 24 - 8 * pass;
-        for (int i = t; i < 256; i += SEL_THREADS) hist[i] = 0;
-        __syncthreads();
-        RunHist rh;
-        int64_t i = t;
-        for (; i + 3 * SEL_THREADS < count; i += 4 * SEL_THREADS) {
-            const uint32_t k0 = keyof(i), k1 = keyof(i + SEL_THREADS), k2 = keyof(i + 2 * SEL_THREADS),
-                           k3 = keyof(i + 3 * SEL_THREADS);
-            if (k0 != 0xFFFFFFFFu && (k0 & mask) == prefix) rh.add(hist, (k0 >> shift) & 255u);
-            if (k1 != 0xFFFFFFFFu && (k1 & mask) == prefix) rh.add(hist, (k1 >> shift) & 255u);
-            if (k2 != 0xFFFFFFFFu && (k2 & mask) == prefix) rh.add(hist, (k2 >> shift) & 255u);
-            if (k3 != 0xFFFFFFFFu && (k3 & mask) == prefix) rh.add(hist, (k3 >> shift) & 255u);
-        }
-        for (; i < count; i += SEL_THREADS) {
-            const uint32_t key = keyof(i);
-            if (key != 0xFFFFFFFFu && (key & mask) == prefix) rh.add(hist, (key >> shift) & 255u);
-        }
-        rh.flush(hist);
-        __syncthreads();
-        hist_pick(hist, kk, pass == 0, sh);
-        __syncthreads();
-        if (sh[0]) {
-            __syncthreads();
-            return 0xFFFFFFFEu;
-        }
-        prefix |= sh[1] << shift;
-        mask |= 255u << shift;
-        kk -= sh[2];
-        __syncthreads();
-    }
-    return PASSES == 4 ? prefix : prefix | (0xFFFFFFFFu >> (8 * PASSES));
+    return radix_passes<NT, PASSES>(
+        [&](auto visit) {
+            int64_t i = threadIdx.x;
+            for (; i + 3 * NT < count; i += 4 * NT) {
+                const uint32_t k0 = keyof(i), k1 = keyof(i + NT), k2 = keyof(i + 2 * NT), k3 = keyof(i + 3 * NT);
+                visit(k0);
+                visit(k1);
+                visit(k2);
+                visit(k3);
+            }
+            for (; i < count; i += NT) visit(keyof(i));
+        },
+        k, hist, sh);
 }
 
 // An upper bound on the k-th smallest valid key of count keys: each thread
@@ -294,31 +285,9 @@ __device__ inline void for_each_f4(const float *row, int64_t P, F &&f) {
 template <int METRIC, int NT = SEL_THREADS>
 __device__ inline uint32_t block_radix_select_rows(const float *row, int64_t P, int k, uint32_t *hist,
                                             uint32_t *sh) {
-    const int t = threadIdx.x;
-    uint32_t prefix = 0, mask = 0, kk = (uint32_t)k;
-    for (int pass = 0; pass < 4; ++pass) {
-        const int shift = 24 - 8 * pass;
-        for (int i = t; i < 256; i += SEL_THREADS) hist[i] = 0;
-        __syncthreads();
-        RunHist rh;
-        for_each_f4<NT>(row, P, [&](int64_t, float raw) {
-            const uint32_t key = key32<METRIC>(raw);
-            if (key != 0xFFFFFFFFu && (key & mask) == prefix) rh.add(hist, (key >> shift) & 255u);
-        });
-        rh.flush(hist);
-        __syncthreads();
-        hist_pick(hist, kk, pass == 0, sh);
-        __syncthreads();
-        if (sh[0]) {
-            __syncthreads();
-            return 0xFFFFFFFEu;
-        }
-        prefix |= sh[1] << shift;
-        mask |= 255u << shift;
-        kk -= sh[2];
-        __syncthreads();
-    }
-    return prefix;
+    return radix_passes<NT, 4>(
+        [&](auto visit) { for_each_f4<NT>(row, P, [&](int64_t, float raw) { visit(key32<METRIC>(raw)); }); }, k,
+        hist, sh);
 }
 
 // ---------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 #!/bin/bash
-# diff_kernel_text.sh [-p PATTERN] PARENT_OBJ... -- BRANCH_OBJ...
+# diff_kernel_text.sh [-r] [-p PATTERN] PARENT_OBJ... -- BRANCH_OBJ...
 #
 # Whether two builds hold the same gfx950 kernels.  Each side is a list of
 # object files (or code objects' hosts: anything with a .hip_fatbin section);
@@ -11,6 +11,10 @@
 #                     the four resource notes: vgpr, sgpr, lds (group segment)
 #                     and scratch (private segment) bytes
 #   MISSING           present on one side only
+#   reordered         (with -r, instead of DIFFERENT) the same instruction lines
+#                     in another order: equal resource notes and identical text
+#                     once both sides' lines are sorted -- a schedule change
+#                     only; not counted as a failure
 # Padding after a kernel's last s_endpgm is not compared when it is only
 # `s_nop 0`, `s_code_end` or `...` lines (it depends on which kernel comes last
 # in an object); anything else there stays in and shows as a difference.
@@ -18,10 +22,16 @@
 set -e -o pipefail
 BIN=${ROCM_PATH:-/opt/rocm}/lib/llvm/bin
 pat=.
-if [ "$1" = "-p" ]; then
-  pat=$2
-  shift 2
-fi
+reorder=0
+while [ "$1" = "-p" ] || [ "$1" = "-r" ]; do
+  if [ "$1" = "-r" ]; then
+    reorder=1
+    shift
+  else
+    pat=$2
+    shift 2
+  fi
+done
 tmp=$(mktemp -d)
 trap 'rm -rf $tmp' EXIT
 mkdir $tmp/1 $tmp/2
@@ -56,7 +66,7 @@ for obj; do
   cat $tmp/notes >> $tmp/$side/notes
 done
 if [ $side = 1 ]; then
-  echo "usage: $0 [-p PATTERN] PARENT_OBJ... -- BRANCH_OBJ..." >&2
+  echo "usage: $0 [-r] [-p PATTERN] PARENT_OBJ... -- BRANCH_OBJ..." >&2
   exit 2
 fi
 # the text up to the last s_endpgm, when only padding follows it
@@ -72,6 +82,7 @@ strip_padding() {
 same=0
 diff=0
 missing=0
+reordered=0
 for name in $(cat $tmp/1/notes $tmp/2/notes | cut -d' ' -f1 | sort -u); do
   pretty=$(echo $name | c++filt)
   n1=$(grep -m1 "^$name " $tmp/1/notes | cut -d' ' -f2- || true)
@@ -86,10 +97,13 @@ for name in $(cat $tmp/1/notes $tmp/2/notes | cut -d' ' -f1 | sort -u); do
   if cmp -s $tmp/a $tmp/b && [ "$n1" = "$n2" ]; then
     echo "same      $(wc -l < $tmp/a) instructions  $n1  $pretty"
     same=$((same + 1))
+  elif [ $reorder = 1 ] && [ "$n1" = "$n2" ] && sort $tmp/a | cmp -s - <(sort $tmp/b); then
+    echo "reordered $(wc -l < $tmp/a) instructions  $n1  $pretty"
+    reordered=$((reordered + 1))
   else
     echo "DIFFERENT $(wc -l < $tmp/a) vs $(wc -l < $tmp/b) instructions  $n1 | $n2  $pretty"
     diff=$((diff + 1))
   fi
 done
-echo "$((same + diff + missing)) kernels: $same same, $diff DIFFERENT, $missing MISSING"
+echo "$((same + reordered + diff + missing)) kernels: $same same, $([ $reorder = 1 ] && echo "$reordered reordered, ")$diff DIFFERENT, $missing MISSING"
 [ $((diff + missing)) = 0 ]
