@@ -20,7 +20,8 @@
 // fragments 0..3 and B fragments 0..7 are in registers.  Phase 0 = row blocks
 // 0..3 x query blocks 0..7; in its gaps the wave reads this stage's A
 // fragments 4..7 and issues its 8 LDS-DMA pieces of stage s + D (gaps 8, 11,
-// .., 29).  It then waits (counted vmcnt) for its own pieces of stage s + 1
+// .., 29) and, in gaps 28 and 30, keeps the ring's books (buffer indices, stage
+// counter).  It then waits (counted vmcnt) for its own pieces of stage s + 1
 // and for its fragment reads (lgkmcnt(0)), and joins ONE raw s_barrier: stage
 // s + 1 is complete for every wave, and every wave is done reading stage
 // s, whose buffer the next phase 0 re-fills (D = NBUF - 1).  Phase 1 =
@@ -95,20 +96,16 @@ constexpr int kP4HiK = 32;         // columns per stage
 // group the (row & 3, slot) pairs are distinct.
 __device__ __host__ inline int p4_g(int x) { return (4 - x) & 3; }
 
-// s_waitcnt vmcnt(P n), n in [0, 3] at run time (P: pieces a wave issues per
-// stage; a stage that also carries a norm piece makes the wait stricter by
-// one operation, never looser)
-template <int P>
-__device__ inline void p4_wait_vm(int n, bool any = true) {
+// s_waitcnt vmcnt(N): all but the wave's N youngest pieces landed.  The ring
+// keeps D stages in flight from the prologue to the end of the launch (dummy
+// stages once every stage is issued: real loads into the free buffer, which
+// nobody reads), so the count is the same immediate at every stage.  A stage
+// that also carries a norm piece makes the wait stricter by one operation,
+// never looser.
+template <int N>
+__device__ inline void p4_wait_vm() {
     __builtin_amdgcn_sched_barrier(0);
-    if (P > 0 && any && n >= 3)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * P) : "memory");
-    else if (P > 0 && any && n == 2)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * P) : "memory");
-    else if (P > 0 && any && n == 1)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(P) : "memory");
-    else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
     __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -335,14 +332,13 @@ __global__ __launch_bounds__(256, 1) void k_scan_p4m(ScanParams p, int slots, u3
     };
     set_src();
     first_src = false;
-    // next stage of the issue item, stages issued (global counter), ring
-    // buffer of the next issued stage
-    int si = 0, issued = 0, ibuf = 0, items_issued = 0;
+    // next stage of the issue item, ring buffer of the next issued stage
+    int si = 0, ibuf = 0, items_issued = 0;
     bool live = true;  // stages left to issue (else: dummy pieces, never read)
     // piece x of the next stage (x < 8; 8 = the L2 norm piece of an item's
     // first stage).  Once every stage is issued the pieces keep going to the
-    // free buffer with the last sources (never read: the ring's counted waits
-    // stay uniform)
+    // free buffer with the last sources (never read: the ring's counted wait
+    // stays the same, p4_wait_vm)
     auto issue_piece = [&](int x) __attribute__((always_inline)) {
         unsigned char *dst = lds + ibuf * kP4Stage;
         if (x < 4) {
@@ -363,37 +359,45 @@ __global__ __launch_bounds__(256, 1) void k_scan_p4m(ScanParams p, int slots, u3
                                              (lds_void *)(norm_lds + (items_issued & 1) * 1024 + w * 256), 4, 0, 0);
         }
     };
-    auto issue_advance = [&]() __attribute__((always_inline)) {
-        if (!live) return;
-        ++issued;
-        ibuf = ibuf + 1 == NBUF ? 0 : ibuf + 1;
-        if (++si == nst) {
-            si = 0;
-            ++items_issued;
-            int r0 = 0, r1 = 0, o = 0;
-            const int tn = next_item(ti_i + tstride, r0, r1, o);
-            if (tn >= 0) {
-                ti_i = tn;
-                ir0 = r0;
-                ir1 = r1;
-                iord = o;
-                set_src();
-            } else {
-                live = false;
-                si = nst - 1;  // dummy pieces re-read the last stage
-            }
+    // after a stage's last piece: the ring half of the advance, without a
+    // branch (it runs in an MFMA gap of phase 0).  Dummy stages keep ibuf (the
+    // free buffer) and si
+    auto advance_ring = [&]() __attribute__((always_inline)) {
+        const int nb_ = ibuf + 1 == NBUF ? 0 : ibuf + 1;
+        ibuf = live ? nb_ : ibuf;
+        si += live ? 1 : 0;
+        asm volatile("" : "+s"(ibuf), "+s"(si));  // (computed here, not sunk to the phase seam)
+    };
+    // the item half: only when the ring advance left si == nst
+    auto advance_item = [&]() __attribute__((always_inline)) {
+        if (si != nst) return;
+        si = 0;
+        ++items_issued;
+        int r0 = 0, r1 = 0, o = 0;
+        const int tn = next_item(ti_i + tstride, r0, r1, o);
+        if (tn >= 0) {
+            ti_i = tn;
+            ir0 = r0;
+            ir1 = r1;
+            iord = o;
+            set_src();
+        } else {
+            live = false;
+            si = nst - 1;  // dummy pieces re-read the last stage
         }
     };
     auto issue_stage = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int x = 0; x < 8; ++x) issue_piece(x);
         if (L2 && si == 0 && live) issue_piece(8);
-        issue_advance();
+        advance_ring();
+        advance_item();
     };
 
     int cr0 = ir0, cr1 = ir1;
     int ti_c = ti_i;
-    int gc = 0, cbuf = 0, items_done = 0;
+    // ring buffer of the stage consumed and of the one after it
+    int cbuf = 0, nbuf_next = 0, items_done = 0;
 
     // fragment offset: image row R = 16 i + (l & 15), chunk l >> 4
     const int offm = l16 * 64 + (g4 ^ p4_g((l16 >> 2) & 3)) * 16;
@@ -410,7 +414,8 @@ __global__ __launch_bounds__(256, 1) void k_scan_p4m(ScanParams p, int slots, u3
     u32x4 *wq_base = queue + (int64_t)(blockIdx.x * 4 + w) * qcap;
 
     for (int s = 0; s < D; ++s) issue_stage();
-    p4_wait_vm<NPW>(issued - 1);
+    // D stages in flight (dummy ones when the launch has fewer): stage 0 landed
+    p4_wait_vm<(D - 1) * NPW>();
     p4_barrier();
     bf16x8 a[8], b[8];
 #pragma unroll
@@ -532,7 +537,7 @@ __global__ __launch_bounds__(256, 1) void k_scan_p4m(ScanParams p, int slots, u3
     };
 
     // phase 0: row blocks 0..3 x query blocks 0..7; in its gaps this stage's
-    // A fragments 4..7, the DMA pieces of stage gc + D and (EPI) the tests of
+    // A fragments 4..7, the DMA pieces of the stage D ahead and (EPI) the tests of
     // the previous item's row blocks 4..7
     auto phase0 = [&](const unsigned char *st, auto first_tag, auto epi_tag) __attribute__((always_inline)) {
         constexpr bool FIRST = decltype(first_tag)::value, EPI = decltype(epi_tag)::value;
@@ -550,6 +555,17 @@ __global__ __launch_bounds__(256, 1) void k_scan_p4m(ScanParams p, int slots, u3
                 a[2 + x] = frag(st, rowA + (2 + x) * 16 * 64 + offm);
             if constexpr (x >= 8 && (x - 8) % 3 == 0 && (x - 8) / 3 < 8)
                 issue_piece((x - 8) / 3);
+            // the ring bookkeeping in gaps that carry no fragment read and no
+            // piece, ahead of the phase's last MFMA (what follows that one
+            // runs with the MFMA pipe draining)
+            if constexpr (x == 28) {
+                nbuf_next = cbuf + 1 == NBUF ? 0 : cbuf + 1;
+                asm volatile("" : "+s"(nbuf_next));
+            }
+            if constexpr (x == 30) {
+                if (L2 && si == 0 && live) issue_piece(8);
+                advance_ring();
+            }
             __builtin_amdgcn_sched_barrier(0);
         });
     };
@@ -582,20 +598,19 @@ __global__ __launch_bounds__(256, 1) void k_scan_p4m(ScanParams p, int slots, u3
 
     auto do_stage = [&](auto first_tag, auto epi_tag, auto last_tag) __attribute__((always_inline)) {
         const unsigned char *st = lds + cbuf * kP4Stage;
-        const int nbuf_next = cbuf + 1 == NBUF ? 0 : cbuf + 1;
         phase0(st, first_tag, epi_tag);
-        if (L2 && si == 0 && live) issue_piece(8);
-        issue_advance();
-        // own pieces of stage gc + 1 landed (younger stages may stay in
-        // flight); this stage's fragment reads retired (the next phase 0
-        // re-fills its buffer); then the barrier: stage gc + 1 is complete
-        // for every wave
-        const bool has_next = gc + 1 < issued;
-        p4_wait_vm<NPW>(issued - gc - 2, has_next);
+        // Between the phases the MFMA pipe runs empty, so only what must be
+        // here is: the item wrap (one compare and branch on most stages),
+        // the two waits and the barrier.
+        advance_item();
+        // own pieces of the next stage landed (the D - 1 younger stages may
+        // stay in flight); this stage's fragment reads retired (the next
+        // phase 0 re-fills its buffer); then the barrier: the next stage is
+        // complete for every wave
+        p4_wait_vm<(D - 1) * NPW>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         p4_barrier();
         phase1(lds + nbuf_next * kP4Stage, first_tag, last_tag, cr1 - cr0);
-        ++gc;
         cbuf = nbuf_next;
     };
 
