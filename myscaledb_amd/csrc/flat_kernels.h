@@ -23,7 +23,9 @@
 //   kernels_qprep.hip    k_query_prep, k_query_prep_lds
 //   kernels_filter.hip   the PREWHERE gather list, chunk ordinals, the decoupled-part filter
 //   kernels_segprep.hip  k_row_norms, k_normalize_rows, k_generate, k_pack
-//   kernels_ingest.hip   the column-file decoder
+//   kernels_ingest.hip   the column files' block table, the array sizes scan, k_array_rows
+//   kernels_lz4.hip      k_decode_blocks (its sequence grammar: lz4_token.h)
+//   kernels_cityhash.hip k_block_checksum
 //   kernels_util.hip     k_fill2, k_words_to_host, k_async_flags, k_map_ids, the HBM read sweep
 // Included by those files (some through select_common.h or scan_emit.h), by
 // index_kernels.h and by workspace.h; the host side the entry points share is
@@ -479,7 +481,8 @@ void launch_generate(uint64_t seed, int mode, int64_t row0, int64_t n, int d, fl
 void launch_pack_nonempty(const uint8_t *bytes, int64_t n, uint8_t *bits, hipStream_t s);
 
 // ---------------------------------------------------------------------------
-// kernels_ingest.hip (column ingest: compressed MergeTree column files -> rows)
+// kernels_ingest.hip, kernels_lz4.hip (launch_decode_blocks), kernels_cityhash.hip
+// (launch_block_checksum): compressed MergeTree column files -> rows; the index blob's framing
 struct IngestBlock {
     int64_t src;      // payload offset in the compressed stream
     int64_t dst;      // offset in the decompressed stream

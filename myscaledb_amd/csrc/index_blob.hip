@@ -16,8 +16,9 @@ namespace mqvs {
 // list, nlist, alpha, np95 -- behind a 64-byte header, framed as a ClickHouse
 // CompressedWriteBuffer stream (include/mqvs.h has the layout byte by byte).
 // Everything else is derived again by finish_index.  The framing reuses the
-// column ingest's device code in both directions: launch_block_table and
-// launch_decode_blocks read it, launch_block_checksum verifies it and, through
+// column ingest's device code in both directions: launch_block_table
+// (kernels_ingest.hip) and launch_decode_blocks (kernels_lz4.hip) read it,
+// launch_block_checksum (kernels_cityhash.hip) verifies it and, through
 // hash_out, computes the checksums the writer stores.
 
 constexpr int64_t kBlobBlock = 1 << 20;  // payload bytes of the blocks mqvs_index_save writes

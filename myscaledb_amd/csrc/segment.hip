@@ -197,7 +197,8 @@ static void fill_empty_result(int64_t m, int64_t *ids, float *dist, uint32_t wor
 
 // ---------------------------------------------------------------------------
 // column ingest: the compressed files of a part's Array(Float32) column,
-// decoded in HBM (kernels_ingest.hip) into the rows matrix + nonempty flags of
+// decoded in HBM (kernels_ingest.hip, kernels_lz4.hip, kernels_cityhash.hip)
+// into the rows matrix + nonempty flags of
 // MergeTreeVSManager.cpp:1381-1393, then prepared like any segment.
 
 struct IngestTmp {

@@ -19,7 +19,7 @@ import numpy as np
 
 from oracle import oracle as O
 
-# the decoder's constants (kernels_ingest.hip) the cases are cut to
+# the decoder's constants (kernels_lz4.hip) the cases are cut to
 K_CHUNK, K_LOOK, K_SEG, K_STARTS = 1024, 256, 16, 4
 K_RING, K_FLUSH, K_GRP_LIT, K_GRP_MATCH, K_MAX_REC = 4096, 1024, 16, 27, 343
 

@@ -7,20 +7,20 @@ stream decodes to those bytes through the oracle and still sits on the edge
 it was built for.
 
 Malformed streams must be refused with ILLEGAL_COLUMN and leave the process
-able to ingest.  The guard each one relies on (kernels_ingest.hip), chunked
-path / token path -- every one of them is checked before any record of the
-chunk (any copy of the sequence) runs, and every store lies below the
-validated output position:
-  off0, off_before_start   pass B `off == 0 || off > o + ll` / `off == 0 || off > op`
-  ll_past_output           pass B `ll > osz - o` / `ll > osz - op`
-  ml_past_output           pass B `ml > osz - o - ll` / `ml > osz - op`
-  lit_past_stream          tok `ll > isz - q` (chain re-parse) / `ll > isz - q`
-  llext_to_end, mlext_to_end  tok `q >= isz` in the extension loops / the same loops
-  half_offset              tok `isz - q < 2` / `isz - q < 2`
-  usize_plus1              the final `op != osz` (both)
-  usize_minus1             pass B `ll > osz - o` at the last literals / `ll > osz - op`
-  ends_in_match            `done` needs the literals-only record / `p >= isz`
-  trailing1, trailing3     tok `isz - q < 2`; pass B `ml > osz - o - ll` / the same two
+able to ingest.  The guard each one relies on: a function of csrc/lz4_token.h,
+which both parse paths go through, or a decoder stage (kernels_lz4.hip) --
+every one of them is checked before any record of the chunk (any copy of the
+sequence) runs, and every store lies below the validated output position:
+  off0, off_before_start   lz4_fits `off == 0 || off > o + ll`
+  ll_past_output           lz4_fits `ll > osz - o`
+  ml_past_output           lz4_fits `ml > osz - o - ll`
+  lit_past_stream          lz4_parse `ll > isz - q`
+  llext_to_end, mlext_to_end  lz4_extend `q >= isz`
+  half_offset              lz4_parse `isz - q < 2`
+  usize_plus1              k_decode_blocks, the final `op != osz`
+  usize_minus1             lz4_fits `ll > osz - o` at the last literals
+  ends_in_match            k_decode_blocks, `done` needs the literals-only sequence
+  trailing1, trailing3     lz4_parse `isz - q < 2`; lz4_fits `ml > osz - o - ll`
 """
 import ctypes
 
